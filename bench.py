@@ -4,11 +4,20 @@
 Default workload (BASELINE.json configs[1], "C2"): a batch of 32 synthetic 1920x1080 NV12 frames,
 device-resident, -> 32x3x512x512 fp32 NCHW normalised (range [0,1], ImageNet mean/std in BGR order),
 one fused kernel launch per step, three steps in flight on three handles / HIP streams (the shape
-PipelineServer's device runner runs by default; `--inflight 1` times one launch at a time, and every
+PipelineServer's device runner runs by default; `--inflight 1` times one launch at a time, and a `--full`
 line carries that one-at-a-time kernel figure as roofline.single_launch). Other configs (--config
 c1|c3|c4|c5) are the remaining BASELINE workloads; the driver's headline line is c2.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2] [--no-cpu-baseline]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, the K timed
+steps, then the result line (value = frames/s, ms_per_step = wall-clock milliseconds per timed step).
+`--dump-outputs DIR` also writes the output tensor of the last timed step to DIR as float32 .npy (the
+whole tensor up to 64 MB, else a fixed seeded sample of its elements); inputs are seeded, so two builds
+run with the same arguments can be compared output for output. `--full` adds every secondary
+measurement, each in launches of its own outside the timed region: the library's byte accounting
+(before the warm-up) and the `roofline` block (single-launch, per-launch spread, resident set),
+`latency`, `host_us_per_call` and the `cpu_baseline` (after it).
 
 Multi-GPU: one process per GPU; camera streams are partitioned s mod G, every rank runs its own batch
 (weak scaling), no collective touches the hot loop; after the timed region one all_reduce(MAX) of the
@@ -22,9 +31,9 @@ stays on-die only while everything touched between two of its uses fits in ~256 
 launches stream from HBM, not from the die-level cache. `--pool 1` re-reads one resident set (the
 round-1 mode); its numbers are reported as the secondary `roofline.resident` field either way.
 
-Output: ONE JSON line from rank 0 with value = frames/s over all ranks, plus `roofline` (algorithmic
-bytes per launch / mean launch time from HIP events on the launch stream) and `cpu_baseline` (the C
-oracle, OpenMP on the host cores, on a bounded sample — rank 0 at N=1 only).
+Output: ONE JSON line from rank 0 with value = frames/s over all ranks, plus, with `--full`, `roofline`
+(algorithmic bytes per launch / mean launch time from HIP events on the launch stream) and `cpu_baseline`
+(the C oracle, OpenMP on the host cores, on a bounded sample — rank 0 at N=1 only).
 """
 from __future__ import annotations
 
@@ -124,6 +133,29 @@ def pool_sets(step_bytes: int, want: int) -> int:
     if want > 0:
         return want
     return max(1, min(64, -(-3 * MALL_BYTES // max(step_bytes, 1))))
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: everything written stays under this
+DUMP_SAMPLE_ELEMS = 4 * 2**20   # elements kept of an output that is larger (16 MiB as float32)
+DUMP_SEED = 20240607
+
+
+def dump_output(torch, out, path: str) -> dict:
+    """Write device tensor `out` to `path` as a float32 .npy: all of it when it fits DUMP_LIMIT_BYTES, else its
+    elements at DUMP_SAMPLE_ELEMS flat indices drawn once from a fixed seed (sorted; the same indices for the same
+    shape in every run and every build). u8 outputs are widened exactly."""
+    flat = out.reshape(-1)
+    n = flat.numel()
+    sampled = n * 4 > DUMP_LIMIT_BYTES
+    if sampled:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE_ELEMS, dtype=np.int64))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arr = flat.to(torch.float32).cpu().numpy()
+    if not sampled:
+        arr = arr.reshape(tuple(out.shape))
+    np.save(path, arr)
+    return {"file": os.path.basename(path), "shape": list(arr.shape), "of_shape": list(out.shape),
+            "sampled": sampled}
 
 
 def cpu_baseline(wl, budget_s: float):
@@ -361,18 +393,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--frames", type=int, default=0, help="frames per rank per step (default: workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement (byte accounting and roofline, "
+                         "single-launch and resident-set figures, per-launch spread, latency, host cost per call, CPU "
+                         "baseline); a plain run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output tensor of the last timed step to DIR/output.npy (output_rank<r>.npy with "
+                         "several ranks) as float32: the whole tensor up to 64 MB, else a fixed seeded sample; for the "
+                         "clip-ring configs the ring slot that step wrote")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--feed", choices=["device", "host"], default="device",
                     help="host: frames start in pinned host memory and cross PCIe every step (SURVEY §8 f3); "
                          "reported as a separate PCIe-inclusive line, never the headline value")
     ap.add_argument("--feed-rows", choices=["touched", "all"], default="touched",
                     help="--feed host: copy only the source rows the resize reads (default) or whole frames")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-baseline work")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU-baseline work")
     ap.add_argument("--pool", type=int, default=0,
                     help="frame/output sets cycled step by step (0: auto, >= 3x the 256 MiB Infinity Cache; "
                          "1: one resident set)")
     ap.add_argument("--resident-steps", type=int, default=200,
-                    help="extra steps on one resident set, reported as roofline.resident (0: skip)")
+                    help="--full: extra steps on one resident set, reported as roofline.resident (0: skip)")
     ap.add_argument("--via", choices=["direct", "pipeline"], default="direct",
                     help="pipeline: drive the workload's frames through PipelineServer (application-source "
                          "pipelines, one per stream, batched across streams by the per-device hub); reported "
@@ -385,7 +425,7 @@ def main():
                     help="launches in flight: step t runs on handle/stream t mod N (independent outputs), so the next "
                          "launches' ramps overlap launch t's tail, timed by wall clock. The default 3 is the shape the "
                          "product runs (PipelineServer's device runner, server option inflight=3); the one-launch-at-"
-                         "a-time kernel figure is reported next to it as roofline.single_launch either way")
+                         "a-time kernel figure is reported next to it as roofline.single_launch by --full either way")
     ap.add_argument("--runner-inflight", type=int, default=3,
                     help="--via pipeline: ticks the device runner keeps in flight (server option inflight)")
     ap.add_argument("--runner", choices=["device", "threads"], default="device",
@@ -514,16 +554,18 @@ def main():
         else:
             pp.convert(batches[k], out, info, rois=roi_sets[t % ROI_SETS] if roi_sets else None)
 
-    # algorithmic bytes per launch, from the library's own accounting
-    pp.set_option(evam.native.OPT_STATS, 1)
-    acc = []
-    for t in range(ROI_SETS if roi_sets else 1):
-        step(t)
-        st = pp.stats()
-        acc.append(int(st.src_bytes + st.dst_bytes))
-    torch.cuda.synchronize()
-    alg_bytes = int(round(sum(acc) / len(acc)))  # mean over the ROI sets a run cycles through
-    pp.set_option(evam.native.OPT_STATS, 0)
+    alg_bytes = 0
+    if args.full:
+        # algorithmic bytes per launch, from the library's own accounting: launches of their own
+        pp.set_option(evam.native.OPT_STATS, 1)
+        acc = []
+        for t in range(ROI_SETS if roi_sets else 1):
+            step(t)
+            st = pp.stats()
+            acc.append(int(st.src_bytes + st.dst_bytes))
+        torch.cuda.synchronize()
+        alg_bytes = int(round(sum(acc) / len(acc)))  # mean over the ROI sets a run cycles through
+        pp.set_option(evam.native.OPT_STATS, 0)
 
     inflight = len(pps) > 1
     for t in range(args.warmup):
@@ -552,94 +594,105 @@ def main():
     if pg:
         dist.barrier()
     wall = time.perf_counter() - t0
-    kern_ms = e0.elapsed_time(e1) / (args.steps - ev_from)  # one launch per step
-    if inflight:  # launches overlap on several streams: the launch rate is the wall-clock step
-        kern_ms = wall / args.steps * 1e3
-    # One launch at a time (the kernel-quality figure, comparable with a rocprof kernel average): back-to-back launches
-    # of the same pooled workload on ONE handle and stream, HIP events on that stream from the end of the first launch
-    # to the end of the last. Without launches in flight this is the timed loop's own event figure.
-    if inflight:
-        n_single = max(args.steps, 100)
-        for t in range(10):
+    dumped = None
+    if args.dump_outputs:
+        # What the last timed step (t = K-1) wrote, before any later launch touches the pool again: its output
+        # tensor, or for a clip ring the slot of every stream's ring that the step filled (the other slots hold
+        # what earlier steps left there).
+        t_last = args.steps - 1
+        last = outs[(t_last % P) % n_out]
+        if ring:
+            last = last[t_last % ring::ring]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "output.npy" if world == 1 else f"output_rank{rank}.npy"
+        dumped = dump_output(torch, last, os.path.join(args.dump_outputs, name))
+    if args.full:
+        kern_ms = e0.elapsed_time(e1) / (args.steps - ev_from)  # one launch per step
+        if inflight:  # launches overlap on several streams: the launch rate is the wall-clock step
+            kern_ms = wall / args.steps * 1e3
+        # One launch at a time (the kernel-quality figure, comparable with a rocprof kernel average): back-to-back
+        # launches of the same pooled workload on ONE handle and stream, HIP events on that stream from the end of the
+        # first launch to the end of the last. Without launches in flight this is the timed loop's own event figure.
+        if inflight:
+            n_single = max(args.steps, 100)
+            for t in range(10):
+                step(t)
+            s0 = torch.cuda.Event(enable_timing=True)
+            s1 = torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            for t in range(n_single):
+                step(t)
+                if t == 0:
+                    s0.record(stream)
+            s1.record(stream)
+            torch.cuda.synchronize()
+            single_ms, single_n = s0.elapsed_time(s1) / (n_single - 1), n_single - 1
+        else:
+            single_ms, single_n = kern_ms, args.steps - ev_from
+        # Per-launch spread (median, p10 / p90), measured after the timed region: one event
+        # pair around each of up to 200 extra steps, so the timed loop above carries no per-step events.
+        n_dist = min(args.steps, 200)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_dist)]
+        for t, (a, b) in enumerate(evs):
+            a.record(stream)
             step(t)
-        s0 = torch.cuda.Event(enable_timing=True)
-        s1 = torch.cuda.Event(enable_timing=True)
+            b.record(stream)
         torch.cuda.synchronize()
-        for t in range(n_single):
-            step(t)
-            if t == 0:
-                s0.record(stream)
-        s1.record(stream)
-        torch.cuda.synchronize()
-        single_ms, single_n = s0.elapsed_time(s1) / (n_single - 1), n_single - 1
-    else:
-        single_ms, single_n = kern_ms, args.steps - ev_from
-    # Per-launch spread (median, p10 / p90), measured after the timed region: one event
-    # pair around each of up to 200 extra steps, so the timed loop above carries no per-step events.
-    n_dist = min(args.steps, 200)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_dist)]
-    for t, (a, b) in enumerate(evs):
-        a.record(stream)
-        step(t)
-        b.record(stream)
-    torch.cuda.synchronize()
-    per = np.sort(np.array([a.elapsed_time(b) for a, b in evs])) if n_dist else np.zeros(1)
-    pct = {q: round(float(np.percentile(per, q)), 5) for q in (10, 50, 90)}
-    # Latency of one batch on an idle device: host enqueue -> kernel done, synchronised per step (the shape a
-    # single camera stream sees; the throughput loop above keeps the device busy instead).
-    n_lat = min(args.steps, 200)
-    lat = []
-    for t in range(n_lat):
-        torch.cuda.synchronize()
-        s0 = time.perf_counter()
-        step(t)
-        torch.cuda.synchronize()
-        lat.append(time.perf_counter() - s0)
-    lat_ms = np.array(lat) * 1e3 if lat else np.zeros(1)
-    latency = {"items": n_items, "steps": n_lat,
-               "ms_p10_p50_p90": [round(float(np.percentile(lat_ms, q)), 4) for q in (10, 50, 90)],
-               "note": "host enqueue to kernel completion per launch, device idle before each"}
-    # Host cost of one call, unthrottled: 12 calls enqueued back to back after a synchronize. That is fewer than
-    # the pinned ROI-record ring's 16 slots, so no call waits for the GPU. host_submit_ms_per_step (the timed loop)
-    # includes those waits: once the host runs 16 calls ahead of a GPU-bound stream, each call waits for the
-    # kernel of 16 calls ago, and host_submit approaches ms_per_step however cheap the call is.
-    host_us = None
-    if feed is None:
-        runs = []
-        for _ in range(20):
+        per = np.sort(np.array([a.elapsed_time(b) for a, b in evs])) if n_dist else np.zeros(1)
+        pct = {q: round(float(np.percentile(per, q)), 5) for q in (10, 50, 90)}
+        # Latency of one batch on an idle device: host enqueue -> kernel done, synchronised per step (the shape a
+        # single camera stream sees; the throughput loop above keeps the device busy instead).
+        n_lat = min(args.steps, 200)
+        lat = []
+        for t in range(n_lat):
             torch.cuda.synchronize()
             s0 = time.perf_counter()
-            for t in range(12):
-                step(t)
-            runs.append((time.perf_counter() - s0) / 12)
-        torch.cuda.synchronize()
-        host_us = round(float(np.median(runs)) * 1e6, 2)
-    # Secondary: the same launches re-reading ONE set (frames and output resident in the Infinity Cache
-    # when they fit), for comparison with the pooled headline.
-    resident = None
-    if args.resident_steps > 0 and feed is None:
-        for t in range(20):
-            step(t, k=0)
-        r0 = torch.cuda.Event(enable_timing=True)
-        r1 = torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        r0.record(stream)
-        for t in range(args.resident_steps):
-            step(t, k=0)
-        r1.record(stream)
-        torch.cuda.synchronize()
-        res_ms = r0.elapsed_time(r1) / args.resident_steps
-        res_gbs = alg_bytes / (res_ms * 1e-3) / 1e9
-        resident = {"achieved": round(res_gbs, 1), "frac": round(res_gbs / HBM_PEAK_GBS, 4),
-                    "mean_launch_ms": round(res_ms, 5), "steps": args.resident_steps,
-                    "set_bytes": in_bytes + out_n * 3 * DH * DW * esz}
+            step(t)
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - s0)
+        lat_ms = np.array(lat) * 1e3 if lat else np.zeros(1)
+        latency = {"items": n_items, "steps": n_lat,
+                   "ms_p10_p50_p90": [round(float(np.percentile(lat_ms, q)), 4) for q in (10, 50, 90)],
+                   "note": "host enqueue to kernel completion per launch, device idle before each"}
+        # Host cost of one call, unthrottled: 12 calls enqueued back to back after a synchronize. That is fewer than
+        # the pinned ROI-record ring's 16 slots, so no call waits for the GPU. host_submit_ms_per_step (the timed
+        # loop) includes those waits: once the host runs 16 calls ahead of a GPU-bound stream, each call waits for
+        # the kernel of 16 calls ago, and host_submit approaches ms_per_step however cheap the call is.
+        host_us = None
+        if feed is None:
+            runs = []
+            for _ in range(20):
+                torch.cuda.synchronize()
+                s0 = time.perf_counter()
+                for t in range(12):
+                    step(t)
+                runs.append((time.perf_counter() - s0) / 12)
+            torch.cuda.synchronize()
+            host_us = round(float(np.median(runs)) * 1e6, 2)
+        # Secondary: the same launches re-reading ONE set (frames and output resident in the Infinity Cache
+        # when they fit), for comparison with the pooled headline.
+        resident = None
+        if args.resident_steps > 0 and feed is None:
+            for t in range(20):
+                step(t, k=0)
+            r0 = torch.cuda.Event(enable_timing=True)
+            r1 = torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            r0.record(stream)
+            for t in range(args.resident_steps):
+                step(t, k=0)
+            r1.record(stream)
+            torch.cuda.synchronize()
+            res_ms = r0.elapsed_time(r1) / args.resident_steps
+            res_gbs = alg_bytes / (res_ms * 1e-3) / 1e9
+            resident = {"achieved": round(res_gbs, 1), "frac": round(res_gbs / HBM_PEAK_GBS, 4),
+                        "mean_launch_ms": round(res_ms, 5), "steps": args.resident_steps,
+                        "set_bytes": in_bytes + out_n * 3 * DH * DW * esz}
     tot = evam.streams.reduce_run(wall, n * args.steps, alg_bytes * args.steps,
                                   device=device if pg and backend == "nccl" else None,
                                   device_key=evam.streams.device_key(local))
     wall_max = tot.elapsed_max_s
     value = tot.frames / wall_max
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    traffic = load_pmc_traffic(args.config, n, P)
 
     if rank == 0:
         res = {
@@ -655,7 +708,6 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(wall_max / args.steps * 1e3, 4),
             "host_submit_ms_per_step": round(t_submit / args.steps * 1e3, 4),
-            "host_us_per_call": host_us,  # unthrottled host cost of one call (see above)
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
@@ -671,24 +723,32 @@ def main():
                                   f"device runner, inflight={len(pps)}): launch t+1's ramp overlaps launch t's tail"
                                   if inflight else "one handle, one HIP stream, launches back to back"),
                        "parallelism": f"streams s mod {world}, one process per GPU, no hot-loop collective"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "algorithmic_bytes_per_launch": alg_bytes, "mean_launch_ms": round(kern_ms, 5),
-                         "event_launches": args.steps - ev_from,
-                         "timing": (f"algorithmic bytes of one step / wall-clock step time, {len(pps)} launches in "
-                                    "flight on separate streams (kernels overlap: a rocprof kernel average is longer "
-                                    "than the step; the one-at-a-time kernel figure is single_launch)"
-                                    if inflight else "HIP events on the launch stream"),
-                         "single_launch": {
-                             "achieved": round(alg_bytes / (single_ms * 1e-3) / 1e9, 1),
-                             "frac": round(alg_bytes / (single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                             "mean_launch_ms": round(single_ms, 5), "launches": single_n,
-                             "timing": "HIP events on one handle's stream, launches back to back, one at a time "
-                                       "(compare with the rocprof kernel average of a one-stream run)"},
-                         "launch_ms_p10_p50_p90": [pct[10], pct[50], pct[90]], "resident": resident},
-            "latency": latency,
         }
-        valu = load_pmc_valu(args.config, n, P) if args.config in VALU_BOUND_CONFIGS else None
+        if dumped is not None:
+            res["outputs"] = dict(dumped, dir=args.dump_outputs, step=args.steps - 1)
+        valu = None
+        if args.full:
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+            traffic = load_pmc_traffic(args.config, n, P)
+            res["host_us_per_call"] = host_us  # unthrottled host cost of one call (see above)
+            res["roofline"] = {
+                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                "algorithmic_bytes_per_launch": alg_bytes, "mean_launch_ms": round(kern_ms, 5),
+                "event_launches": args.steps - ev_from,
+                "timing": (f"algorithmic bytes of one step / wall-clock step time, {len(pps)} launches in "
+                           "flight on separate streams (kernels overlap: a rocprof kernel average is longer "
+                           "than the step; the one-at-a-time kernel figure is single_launch)"
+                           if inflight else "HIP events on the launch stream"),
+                "single_launch": {
+                    "achieved": round(alg_bytes / (single_ms * 1e-3) / 1e9, 1),
+                    "frac": round(alg_bytes / (single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                    "mean_launch_ms": round(single_ms, 5), "launches": single_n,
+                    "timing": "HIP events on one handle's stream, launches back to back, one at a time "
+                              "(compare with the rocprof kernel average of a one-stream run)"},
+                "launch_ms_p10_p50_p90": [pct[10], pct[50], pct[90]], "resident": resident}
+            res["latency"] = latency
+            valu = load_pmc_valu(args.config, n, P) if args.config in VALU_BOUND_CONFIGS else None
         if valu:
             # integer-issue-bound workload: the roofline that bounds it is the VALU issue rate; the HBM
             # figures stay as a secondary block
@@ -713,7 +773,7 @@ def main():
                                   "with the kernel (depth-3 ring; rows=touched: only the source rows the resize "
                                   "reads, as strided 2-D copies unless they cover >= 85% of the frame); "
                                   "roofline.mean_launch_ms includes copy waits"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(wl, args.cpu_budget)
         else:
             res["cpu_baseline"] = None

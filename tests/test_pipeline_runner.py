@@ -499,24 +499,30 @@ def test_runner_failed_stream_gets_nothing_after_its_marker(stubbed):
     register(ps, det_every=1)
     qa, qb, outa, outb = queue.Queue(), queue.Queue(), queue.Queue(), queue.Queue()
     pa, pb = (ps.PipelineServer.pipeline("detect", "hip") for _ in range(2))
-    for p, qin, qout in ((pa, qa, outa), (pb, qb, outb)):
-        p.start(source={"type": "application", "input": qin},
-                destination={"metadata": {"type": "application", "output": qout, "mode": "json"}},
-                parameters={"detection-properties": {"batch-size": 2}})
-    st = pa.stages[0]
-    orig, calls = st.prepare, [0]
+    assert pa.slot == pb.slot
+    calls = [0]
+    # The runner thread takes its condition to look at its pipelines: holding it until both streams are started,
+    # patched and fed makes the first tick see both of them whole, so it takes batch_max / 2 = 2 frames of each
+    # however the threads are scheduled (a runner that saw A's frames before B's took 4 of A's in its first tick).
+    with ps._SERVER.runner(pa.slot)._cv:
+        for p, qin, qout in ((pa, qa, outa), (pb, qb, outb)):
+            p.start(source={"type": "application", "input": qin},
+                    destination={"metadata": {"type": "application", "output": qout, "mode": "json"}},
+                    parameters={"detection-properties": {"batch-size": 2}})
+        st = pa.stages[0]
+        orig = st.prepare
 
-    def prepare(items):
-        calls[0] += 1
-        if calls[0] == 2:
-            raise RuntimeError("prepare failed on A's second tick")
-        return orig(items)
+        def prepare(items):
+            calls[0] += 1
+            if calls[0] == 2:
+                raise RuntimeError("prepare failed on A's second tick")
+            return orig(items)
 
-    st.prepare = prepare
-    for qin in (qa, qb):
-        for im in frames(pre, 8):
-            qin.put(im)
-        qin.put(None)
+        st.prepare = prepare
+        for qin in (qa, qb):
+            for im in frames(pre, 8):
+                qin.put(im)
+            qin.put(None)
     assert pb.wait(30)["state"] == "COMPLETED"
     sa = pa.wait(30)
     assert sa["state"] == "ERROR" and "second tick" in sa.get("message", ""), sa

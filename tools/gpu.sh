@@ -64,14 +64,14 @@ for st in "$@"; do
       n=1; [ "$arg" != "$st" ] && n="$arg"
       for k in $(seq 1 "$n"); do
         sfx=""; [ "$n" -gt 1 ] && sfx="_$k"
-        timeout -k 10 240 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_${TAG}_driver$sfx.json" \
+        timeout -k 10 240 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_${TAG}_driver$sfx.json" \
           2> "$OUT/bench_${TAG}_driver$sfx.err" || { tail -20 "$OUT/bench_${TAG}_driver$sfx.err"; exit 1; }
         tail -1 "$OUT/bench_${TAG}_driver$sfx.json"
       done ;;
     feed)
       # PCIe-inclusive lines: frames start in pinned host memory (f3 host feed, touched-rows plan)
       for c in $cfgs; do
-        timeout -k 10 300 python3 bench.py --config "$c" --steps 300 --warmup 30 --feed host --no-cpu-baseline \
+        timeout -k 10 300 python3 bench.py --config "$c" --steps 300 --warmup 30 --feed host --full --no-cpu-baseline \
           > "$OUT/bench_${TAG}_feed_$c.json" 2> "$OUT/bench_${TAG}_feed_$c.err" || { tail -20 "$OUT/bench_${TAG}_feed_$c.err"; exit 1; }
         tail -1 "$OUT/bench_${TAG}_feed_$c.json"
       done ;;
@@ -89,7 +89,7 @@ for st in "$@"; do
       done ;;
     bench)
       for c in $cfgs; do
-        timeout -k 10 300 python3 bench.py --config "$c" --steps "${BENCH_STEPS:-1000}" --warmup 100 $CPUARG \
+        timeout -k 10 300 python3 bench.py --config "$c" --steps "${BENCH_STEPS:-1000}" --warmup 100 --full $CPUARG \
           ${BENCH_ARGS:-} > "$OUT/bench_${TAG}_$c.json" 2> "$OUT/bench_${TAG}_$c.err" || { tail -20 "$OUT/bench_${TAG}_$c.err"; exit 1; }
         python3 - "$OUT/bench_${TAG}_$c.json" "$c" <<'PY' | tee -a "$OUT/bench_$TAG.txt"
 import json, sys
@@ -130,7 +130,7 @@ PY
       # -DEVAM_PP_HOST_PROF before the call), one launch at a time, plus the bench's own host_us_per_call
       for c in $cfgs; do
         EVAM_PP_LIB=ab/libevam_pp_hostprof.so timeout -k 10 200 python3 bench.py --config "$c" --steps 1000 --warmup 100 \
-          --no-cpu-baseline --inflight 1 > "$OUT/hostprof_${TAG}_$c.json" 2> "$OUT/hostprof_${TAG}_$c.err" \
+          --full --no-cpu-baseline --inflight 1 > "$OUT/hostprof_${TAG}_$c.json" 2> "$OUT/hostprof_${TAG}_$c.err" \
           || { tail -20 "$OUT/hostprof_${TAG}_$c.err"; exit 1; }
         echo "$c $(grep 'host prof' "$OUT/hostprof_${TAG}_$c.err") host_us_per_call $(python3 -c "import json; print(json.loads(open('$OUT/hostprof_${TAG}_$c.json').read().splitlines()[-1])['host_us_per_call'])")" \
           | tee -a "$OUT/hostprof_$TAG.txt"
@@ -140,7 +140,7 @@ PY
       bash tools/gpu_env_ab.sh "$TAG" "$c" "$sets" ;;
     dist)
       EVAM_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 100 --warmup 20 \
+        --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 100 --warmup 20 --full \
         > "$OUT/bench_dist2_$TAG.json" 2> "$OUT/bench_dist2_$TAG.err" || { tail -20 "$OUT/bench_dist2_$TAG.err"; exit 1; }
       tail -1 "$OUT/bench_dist2_$TAG.json" ;;
     *) echo "unknown step $st"; exit 2 ;;
