@@ -8,14 +8,15 @@ The directory name contains hyphens, so import it with importlib::
 After the first import the package is also reachable as ``evam_amd`` (``sys.modules`` alias).
 
 Scope: decoded NV12/I420/BGRx/BGR frames -> colour conversion -> INTER_LINEAR /
-letterbox / central-crop resize -> ROI crop-resize -> normalisation -> NCHW batch packing, as hand-written
-HIP kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
+letterbox / central-crop resize -> ROI crop-resize -> normalisation -> NCHW (planar) or NHWC (interleaved:
+``torch.channels_last`` tensors, ``HipPreProcessor.export_bgr`` frames) batch packing, as hand-written HIP
+kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
 """
 import sys as _sys
 
 from ._native import PreProcError, load_library  # noqa: F401
 from .preproc import (HipPreProcessor, Image, ImageBatch, PreProcInfo, Roi, RoiBatch, Transform,  # noqa: F401
-                      create_preprocessor, plane_layout)
+                      create_preprocessor, plane_layout, tensor_layout)
 from . import _native as native  # noqa: F401
 from . import streams  # noqa: F401
 from . import postproc  # noqa: F401

@@ -44,10 +44,11 @@ RESIZE_NO_ASPECT, RESIZE_ASPECT, RESIZE_ASPECT_CROP = 0, 1, 2
 PLACE_TOP_LEFT, PLACE_CENTER = 0, 1
 COLOR_BGR, COLOR_RGB = 0, 1
 DTYPE_U8, DTYPE_F32 = 0, 1
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 NORM_RANGE, NORM_MEAN_STD = 1, 2
 OPT_STATS, OPT_TIMING = 1, 2
 
-ABI_VERSION = 2  # 2: evam_pp_run_slots
+ABI_VERSION = 3  # 2: evam_pp_run_slots; 3: evam_tensor.layout
 
 # Every symbol include/evam_pp.h declares.
 EXPORTED_SYMBOLS = (
@@ -76,7 +77,7 @@ class EvamPreproc(ctypes.Structure):
 
 class EvamTensor(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("n", c_i32), ("c", c_i32), ("h", c_i32), ("w", c_i32),
-                ("slot_offset", c_i32), ("slot_stride", c_i32)]
+                ("slot_offset", c_i32), ("slot_stride", c_i32), ("layout", c_i32), ("reserved", c_i32)]
 
 
 class EvamTransform(ctypes.Structure):
@@ -95,7 +96,7 @@ KERNEL_GENERIC, KERNEL_ROWS, KERNEL_STAGED, KERNEL_WAVE = 1, 2, 4, 8
 KERNEL_STRIP, KERNEL_BAND, KERNEL_ROI = 16, 32, 64
 
 
-STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 32, EvamTransform: 40, EvamStats: 32}
+STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32}
 
 _LIB = None
 

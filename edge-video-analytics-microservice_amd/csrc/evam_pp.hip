@@ -17,7 +17,9 @@
 //         with 128-bit coalesced loads;
 //      3. for every output pixel converts its four taps to BGR (BT.601 20-bit fixed point), runs the
 //         11-bit horizontal pass and the VResizeLinear 32s->8u vertical pass, maps the u8 result
-//         through the per-channel normalisation LUT (fp32 out) and stores planar NCHW.
+//         through the per-channel normalisation LUT (fp32 out) and stores planar NCHW, or, for a tensor with
+//         layout = EVAM_LAYOUT_NHWC, the slot's interleaved H x W x 3 image (a NHWC template parameter on the
+//         strip, band, wave and generic kernels: only the store epilogue differs).
 //  * Letterbox padding tiles never touch the source. Nothing is MFMA-shaped: the path is HBM-bound
 //    integer gather work (roofline: HBM, 8 TB/s).
 #include <hip/hip_runtime.h>
@@ -271,10 +273,24 @@ __device__ __forceinline__ void to_bgr(const uint32_t (&v)[3], int& b, int& g, i
 
 // Planar stores of one pixel. Plane bases are wave-uniform (SGPR) and the offset is a 32-bit byte
 // offset, so every store is one saddr-form instruction with no 64-bit address arithmetic.
-template <int OUT>
+// NHWC (interleaved output): d0 is the slot base and the pixel's three elements are adjacent at 3 * o
+// (d1, d2 unused); element stores only, so a slot may start at any element-aligned address.
+template <int OUT, bool NHWC = false>
 __device__ __forceinline__ void store_px(uint8_t* d0, uint8_t* d1, uint8_t* d2, const float* __restrict__ lut,
                                          uint32_t o, int v0, int v1, int v2) {
-    if constexpr (OUT == 0) {
+    if constexpr (NHWC) {
+        const uint32_t o3 = o * 3u;
+        if constexpr (OUT == 0) {
+            d0[o3] = (uint8_t)v0;
+            d0[o3 + 1] = (uint8_t)v1;
+            d0[o3 + 2] = (uint8_t)v2;
+        } else {
+            float* const q = reinterpret_cast<float*>(d0 + (o3 << 2));
+            q[0] = lut[v0];
+            q[1] = lut[256 + v1];
+            q[2] = lut[512 + v2];
+        }
+    } else if constexpr (OUT == 0) {
         d0[o] = (uint8_t)v0;
         d1[o] = (uint8_t)v1;
         d2[o] = (uint8_t)v2;
@@ -292,7 +308,7 @@ __device__ __forceinline__ void store_px(uint8_t* d0, uint8_t* d1, uint8_t* d2, 
 // bytes through L1, adjacent lanes sharing cache lines — converts them to BGR, runs both resize passes,
 // maps the u8 result through the normalisation LUT and stores the three planes. No staging, no barrier
 // after the tables: the memory pipeline overlaps loads of many pixels and many waves.
-template <int FMT, int OUT>
+template <int FMT, int OUT, bool NHWC = false>
 __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     using T = FmtTraits<FMT>;
@@ -408,7 +424,7 @@ __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
     auto finish = [&](const Px& x) {
         if (x.mode == 0) return;
         if (x.mode == 1) {
-            if (!(kAblate & 4)) store_px<OUT>(d0, d1, d2, lut_s, x.o, f0, f1, f2);
+            if (!(kAblate & 4)) store_px<OUT, NHWC>(d0, d1, d2, lut_s, x.o, f0, f1, f2);
             return;
         }
         if (kAblate & 8) {  // diagnostics: loads only, trivial math
@@ -437,9 +453,9 @@ __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
             return;
         }
         if (P.color_rgb)
-            store_px<OUT>(d0, d1, d2, lut_s, x.o, vr, vg, vb);
+            store_px<OUT, NHWC>(d0, d1, d2, lut_s, x.o, vr, vg, vb);
         else
-            store_px<OUT>(d0, d1, d2, lut_s, x.o, vb, vg, vr);
+            store_px<OUT, NHWC>(d0, d1, d2, lut_s, x.o, vb, vg, vr);
     };
     if (tid >= npx) return;
     Px cur, nxt;
@@ -1186,6 +1202,7 @@ struct WParams {
 };
 
 typedef int evam_v2i __attribute__((ext_vector_type(2)));
+typedef int evam_v3i __attribute__((ext_vector_type(3)));
 typedef int evam_v4i __attribute__((ext_vector_type(4)));
 
 // PX adjacent output pixels of one channel from one lane: a single buffer store of PX x 4 bytes (fp32)
@@ -1254,8 +1271,13 @@ __device__ __forceinline__ void store_off(const __amdgpu_buffer_rsrc_t rs, uint3
 //    row that the previous output row already filtered is neither staged nor converted again.
 //  * When both vertical taps read the same 4:2:0 chroma row, its BT.601 chroma terms are computed once.
 //  * Each channel of a row leaves as one PX-wide store per lane (dwordx4 for fp32 at PX = 4).
-template <int FMT, int OUT, int PX, bool REUSE>
+//  * NHWC (interleaved output, PX = 4): a lane's four pixels are 12 adjacent elements of the slot, so a row leaves as
+//    one 12-byte store per lane (u8) or three 16-byte stores (fp32) that cover 3 KB contiguous per wave. The host
+//    takes this variant only where every such store is aligned to its width: DW % 4 == 0 makes every row and slot
+//    size a multiple of it, so the tensor's base address decides (4 bytes for u8, 16 for fp32).
+template <int FMT, int OUT, int PX, bool REUSE, bool NHWC = false>
 __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
+    static_assert(!NHWC || PX == 4, "the interleaved store is written for four pixels per lane");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     using T = FmtTraits<FMT>;
     constexpr bool kYUV = FMT == kNV12 || FMT == kI420;
@@ -1287,8 +1309,8 @@ __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
     const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p0, (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(p1 ? p1 : p0), (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)(p2 ? p2 : p0), (short)0, 0x7FFFFFFF, 0x00020000);
-    // output planes in store order (BGR, or RGB: planes 0 and 2 exchanged)
-    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(P.color_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
+    // output planes in store order (BGR, or RGB: planes 0 and 2 exchanged); NHWC: rsO0 is the whole slot
+    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(!NHWC && P.color_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO1 = __builtin_amdgcn_make_buffer_rsrc((void*)d1, (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO2 = __builtin_amdgcn_make_buffer_rsrc((void*)(P.color_rgb ? d0 : d2), (short)0, 0x7FFFFFFF, 0x00020000);
 
@@ -1421,6 +1443,35 @@ __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
         // exempt from the compiler's store-data hazard check, yet on gfx950 a VALU write right after
         // such a dwordx4 store corrupted the stored data (lanes 12-15 of each 16, first dword);
         // with soffset 0 the compiler inserts the wait state.
+        if constexpr (NHWC) {
+            // the lane's 12 elements in output channel order (RGB: B and R exchanged per pixel); the LUT sections
+            // are per OUTPUT channel, so channel c of the output reads section c
+            const uint32_t off3 = (vo + (uint32_t)(Y * P.DW) * (uint32_t)esz) * 3u;
+            int e[3 * PX];
+#pragma unroll
+            for (int j = 0; j < PX; j++) {
+                e[3 * j] = P.color_rgb ? v[2][j] : v[0][j];
+                e[3 * j + 1] = v[1][j];
+                e[3 * j + 2] = P.color_rgb ? v[0][j] : v[2][j];
+            }
+            if constexpr (OUT == 1) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    evam_v4i q;
+#pragma unroll
+                    for (int m = 0; m < 4; m++) q[m] = (int)__float_as_uint(lut_s[((4 * k + m) % 3) * 256 + e[4 * k + m]]);
+                    __builtin_amdgcn_raw_buffer_store_b128(q, rsO0, off3 + 16u * k, 0, EVAM_PP_STORE_AUX);
+                }
+            } else {
+                evam_v3i q;
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    q[k] = (int)((uint32_t)e[4 * k] | ((uint32_t)e[4 * k + 1] << 8) | ((uint32_t)e[4 * k + 2] << 16) |
+                                 ((uint32_t)e[4 * k + 3] << 24));
+                __builtin_amdgcn_raw_buffer_store_b96(q, rsO0, off3, 0, EVAM_PP_STORE_AUX);
+            }
+            return;
+        }
         const uint32_t off = vo + (uint32_t)(Y * P.DW) * (uint32_t)esz;
         // the LUT is per output plane: B lands in plane 2 when the output is RGB
         store_vec<OUT, PX>(rsO0, off, 0, lut_s + (P.color_rgb ? 512 : 0), v[0]);
@@ -1462,8 +1513,10 @@ __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
     }
     int i = 0;
     for (int Y = Yw0; Y < Yw1; Y++, i++) {
-        // this row's DMA landed; the previous row's three stores may stay in flight
+        // this row's DMA landed; the previous row's stores (three, or the single 12-byte one of u8 NHWC) may stay
+        // in flight
         if (i == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if constexpr (NHWC && OUT == 0) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         const uint8_t* buf = wbuf + (i & 1) * half;
         const int na = cur.pad ? pa : cur.ya, nb = cur.pad ? pb : cur.yb;
@@ -1669,8 +1722,13 @@ struct ProgressPrio {
     }
 };
 
-template <int FMT, int OUT, int D, int PX, int PR>
+// NHWC (interleaved fp32 output): a pixel's three values leave as one 12-byte store, so a store instruction covers
+// 768 contiguous bytes of the row where the planar one covers 256 in each of three planes, and a row costs one
+// store per pixel column group instead of three. (u8 would be 3-byte stores per lane: the wave kernel serves it.)
+template <int FMT, int OUT, int D, int PX, int PR, bool NHWC = false>
 __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
+    static_assert(!NHWC || OUT == 1, "the interleaved strip store is fp32 only");
+    constexpr int NS = NHWC ? 1 : 3;  // stores per pixel column group and row
     // the LUT at a static LDS address (folds into the reads' immediate offsets); the rings after it
     __shared__ __attribute__((aligned(16))) float lut_s[OUT == 1 ? 768 : 4];
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1839,7 +1897,7 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     for (int j = 0; j < PX; j++) {
         const int X = X0 + lane + 64 * j;
         xin[j] = live && X < p_DW;
-        vo[j] = (uint32_t)(xin[j] ? X : 0) * (uint32_t)esz;
+        vo[j] = (uint32_t)(xin[j] ? X : 0) * (uint32_t)(NHWC ? 3 * esz : esz);
         lY[j] = lC0[j] = lC1[j] = wp[j] = 0;
         padc[j] = true;
         const int dx = X - g_ox;
@@ -1870,8 +1928,8 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)(P.slot_offset + index * P.slot_stride) * 3 * plane * esz;
     uint8_t* const d1 = d0 + plane * esz;
     uint8_t* const d2 = d1 + plane * esz;
-    // output planes in source channel order (B, G, R): planes 0 and 2 exchanged for RGB
-    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
+    // output planes in source channel order (B, G, R): planes 0 and 2 exchanged for RGB; NHWC: rsO0 is the whole slot
+    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(!NHWC && k_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO1 = __builtin_amdgcn_make_buffer_rsrc((void*)d1, (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO2 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d0 : d2), (short)0, 0x7FFFFFFF, 0x00020000);
     // fill in source channel order (P.fill is in output plane order)
@@ -1928,6 +1986,16 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
             asm volatile("" ::"v"(v0), "v"(v1), "v"(v2));
             return;
         }
+        if constexpr (NHWC) {
+            // the LUT sections are in source channel order (loaded swapped for RGB), the store in output order; the
+            // row offset goes in the VGPR offset (soffset 0: the store-data hazard of wide stores, see evam_pp_wave)
+            const int l0 = (int)*reinterpret_cast<const uint32_t*>(lutb + v0);
+            const int l1 = (int)*reinterpret_cast<const uint32_t*>(lutb + 1024 + v1);
+            const int l2 = (int)*reinterpret_cast<const uint32_t*>(lutb + 2048 + v2);
+            const evam_v3i q = {k_rgb ? l2 : l0, l1, k_rgb ? l0 : l2};
+            __builtin_amdgcn_raw_buffer_store_b96(q, rsO0, vo[j] + (uint32_t)(Y * p_DW) * 12u, 0, EVAM_PP_STORE_AUX);
+            return;
+        }
         const int so = (int)((uint32_t)(Y * p_DW) * (uint32_t)esz);
         if constexpr (OUT == 1) {
             __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + v0), rsO0, vo[j], so, EVAM_PP_STORE_AUX);
@@ -1951,7 +2019,7 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     // workgroups' waves lag and end the launch alone; a wave lowers its priority as it passes each quarter of its
     // rows, so the ones behind get the issue slots when several are ready.
     ProgressPrio prio(P.prio != 0, n);
-    const int nst = full ? 3 * PX : 3;
+    const int nst = full ? NS * PX : NS;
     // one output row: row i of the tile's visible rows, ring entry kk (compile-time after unrolling)
     auto row = [&](int i, int kk, auto has_pad) {
         constexpr bool PADC = decltype(has_pad)::value;
@@ -1961,8 +2029,8 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
         if (SD == 0) {  // nothing was issued after row i's DMA
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else if (i >= SD && i + D - 1 < n) {
-            if (PX == 1 || !full) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NMIN + SD * 3) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NMIN + SD * 3 * PX) : "memory");
+            if (PX == 1 || !full) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NMIN + SD * NS) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NMIN + SD * NS * PX) : "memory");
         } else {
             vmcnt_exact(NMIN * (min(i + D - 1, n - 1) - i) + nst * min(i, SD));
         }
@@ -2162,8 +2230,13 @@ __device__ __forceinline__ void vmcnt_le(int n) {
 //    source row costs 6 luma and 18 saturating sums instead of 8 and 24, a chroma row 3 conversions instead of 8;
 //  * each channel of a row leaves as one PX-wide store per lane.
 // Workgroups of up to four waves: the strips of one band of one item.
-template <int FMT, int OUT, int PX, int DD>
+// NHWC (interleaved u8 output, PX = 4): a lane's four pixels are 12 adjacent bytes of the slot, packed from the
+// same sums into three dwords and stored as one 12-byte store per row (the host admits it where that store is
+// dword-aligned: DW % 4 == 0 and a 4-byte-aligned tensor base).
+template <int FMT, int OUT, int PX, int DD, bool NHWC = false>
 __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
+    static_assert(!NHWC || (OUT == 0 && PX == 4), "the interleaved band store is u8 at four pixels per lane");
+    constexpr int NS = NHWC ? 1 : 3;  // stores per output row
     __shared__ __attribute__((aligned(16))) float lut_s[OUT == 1 ? 768 : 4];
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     if (kAblate & 128) return;  // diagnostics: launch cost only
@@ -2313,12 +2386,13 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
         return;
     }
     const size_t esz = OUT == 1 ? 4 : 1;
-    const uint32_t vo = (uint32_t)(xin ? X : 0) * (uint32_t)esz;
+    const uint32_t vo = (uint32_t)(xin ? X : 0) * (uint32_t)(NHWC ? 3 * esz : esz);
     const size_t plane = (size_t)p_DW * p_DH;
     uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)(P.slot_offset + it.index * P.slot_stride) * 3 * plane * esz;
     uint8_t* const d1 = d0 + plane * esz;
     uint8_t* const d2 = d1 + plane * esz;
-    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
+    // (NHWC: rsO0 is the whole slot)
+    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(!NHWC && k_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO1 = __builtin_amdgcn_make_buffer_rsrc((void*)d1, (short)0, 0x7FFFFFFF, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsO2 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d0 : d2), (short)0, 0x7FFFFFFF, 0x00020000);
     const uint32_t fq0 = P.fill & 0xFF, fq1 = (P.fill >> 8) & 0xFF, fq2 = (P.fill >> 16) & 0xFF;
@@ -2327,8 +2401,32 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
     const uint8_t* lutb = reinterpret_cast<const uint8_t*>(lut_s);
     // one row of the strip: v[c][j] = LUT byte offsets (fp32) or bytes (u8) in source channel order; the
     // row offset in the VGPR offset (soffset 0: the store-data hazard of wide stores, see evam_pp_wave)
+    // NHWC: the lane's 12 bytes of row Y from the sums x (byte = x >> 2), source channel order in, output order out
+    auto put_nhwc = [&](int Y, const uint32_t (&x)[3][PX]) {
+        if constexpr (NHWC) {
+            if (!xin) return;
+            uint32_t a[4], c[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                a[j] = k_rgb ? x[2][j] : x[0][j];
+                c[j] = k_rgb ? x[0][j] : x[2][j];
+            }
+            const evam_v3i q = {(int)pack4_u8_sums(a[0], x[1][0], c[0], a[1]), (int)pack4_u8_sums(x[1][1], c[1], a[2], x[1][2]),
+                                (int)pack4_u8_sums(c[2], a[3], x[1][3], c[3])};
+            __builtin_amdgcn_raw_buffer_store_b96(q, rsO0, vo + (uint32_t)(Y * p_DW) * 3u, 0, EVAM_PP_STORE_AUX);
+        }
+    };
     auto put = [&](int Y, const uint32_t (&v)[3][PX]) {
         if (!xin) return;
+        if constexpr (NHWC) {
+            uint32_t x[3][PX];
+#pragma unroll
+            for (int j = 0; j < PX; j++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) x[c][j] = v[c][j] << 2;
+            put_nhwc(Y, x);
+            return;
+        }
         const uint32_t off = vo + (uint32_t)(Y * p_DW) * (uint32_t)esz;
         store_off<OUT, PX>(rsO0, off, lutb, v[0]);
         store_off<OUT, PX>(rsO1, off, lutb + 1024, v[1]);
@@ -2342,7 +2440,7 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
     };
     for (int Y = Y0; Y < (n ? vr0 : Y1); Y++) {  // letterbox rows above
         put_fill(Y);
-        pos += 3;
+        pos += NS;
     }
 
     uint32_t kb = kKBs, kg = kKGs, kr = kKRs;
@@ -2434,7 +2532,7 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
     };
     HRow HA, HB;
     int pa = -1, pb = -1;
-    const int nst = 3;  // stores per output row (one PX-wide store per channel)
+    const int nst = NS;  // stores per output row (one PX-wide store per channel; NHWC: one for all three)
     // progress-based priority (EVAM_PP_PRIO), as in the strip kernel
     ProgressPrio prio(P.prio != 0, n);
     for (int i = 0; i < n; i++) {
@@ -2491,7 +2589,9 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
                     x[2][j] = padc[j] ? fill2 << 2 : x[2][j];
                 }
             }
-            if (xin) {
+            if constexpr (NHWC) {
+                put_nhwc(vr0 + i, x);
+            } else if (xin) {
                 const uint32_t off = vo + (uint32_t)((vr0 + i) * p_DW);
                 __builtin_amdgcn_raw_buffer_store_b32(pack4_u8_sums(x[0][0], x[0][1], x[0][2], x[0][3]), rsO0, off, 0,
                                                       EVAM_PP_STORE_AUX);
@@ -3166,6 +3266,17 @@ hipError_t launch_t(const KParams& p, int grid, int lds, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Interleaved (NHWC) output: the same kernel with the interleaved store epilogue.
+template <int FMT, int OUT>
+hipError_t launch_nhwc_t(const KParams& p, int grid, int lds, hipStream_t s) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)evam_pp_kernel<FMT, OUT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((evam_pp_kernel<FMT, OUT, true>), dim3(grid), dim3(kThreads), lds, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch(int f, int out, const KParams& p, int grid, int lds, hipStream_t s) {
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return launch_t<kNV12, 0>(p, grid, lds, s);
@@ -3176,6 +3287,19 @@ hipError_t launch(int f, int out, const KParams& p, int grid, int lds, hipStream
     case kBGRX * 2 + 1: return launch_t<kBGRX, 1>(p, grid, lds, s);
     case kBGR * 2 + 0: return launch_t<kBGR, 0>(p, grid, lds, s);
     default: return launch_t<kBGR, 1>(p, grid, lds, s);
+    }
+}
+
+hipError_t launch_nhwc(int f, int out, const KParams& p, int grid, int lds, hipStream_t s) {
+    switch (f * 2 + out) {
+    case kNV12 * 2 + 0: return launch_nhwc_t<kNV12, 0>(p, grid, lds, s);
+    case kNV12 * 2 + 1: return launch_nhwc_t<kNV12, 1>(p, grid, lds, s);
+    case kI420 * 2 + 0: return launch_nhwc_t<kI420, 0>(p, grid, lds, s);
+    case kI420 * 2 + 1: return launch_nhwc_t<kI420, 1>(p, grid, lds, s);
+    case kBGRX * 2 + 0: return launch_nhwc_t<kBGRX, 0>(p, grid, lds, s);
+    case kBGRX * 2 + 1: return launch_nhwc_t<kBGRX, 1>(p, grid, lds, s);
+    case kBGR * 2 + 0: return launch_nhwc_t<kBGR, 0>(p, grid, lds, s);
+    default: return launch_nhwc_t<kBGR, 1>(p, grid, lds, s);
     }
 }
 
@@ -3243,6 +3367,27 @@ hipError_t launch_wave(int f, int out, int px, bool reuse, const WParams& p, int
     }
 }
 
+// Interleaved (NHWC) output: PX = 4 only (the planner takes nothing else), see evam_pp_wave.
+template <int FMT, int OUT>
+hipError_t launch_wave_nhwc_t(bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
+    if (reuse) hipLaunchKernelGGL((evam_pp_wave<FMT, OUT, 4, true, true>), dim3(grid), dim3(kThreads), lds, s, p);
+    else hipLaunchKernelGGL((evam_pp_wave<FMT, OUT, 4, false, true>), dim3(grid), dim3(kThreads), lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_wave_nhwc(int f, int out, bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
+    switch (f * 2 + out) {
+    case kNV12 * 2 + 0: return launch_wave_nhwc_t<kNV12, 0>(reuse, p, grid, lds, s);
+    case kNV12 * 2 + 1: return launch_wave_nhwc_t<kNV12, 1>(reuse, p, grid, lds, s);
+    case kI420 * 2 + 0: return launch_wave_nhwc_t<kI420, 0>(reuse, p, grid, lds, s);
+    case kI420 * 2 + 1: return launch_wave_nhwc_t<kI420, 1>(reuse, p, grid, lds, s);
+    case kBGRX * 2 + 0: return launch_wave_nhwc_t<kBGRX, 0>(reuse, p, grid, lds, s);
+    case kBGRX * 2 + 1: return launch_wave_nhwc_t<kBGRX, 1>(reuse, p, grid, lds, s);
+    case kBGR * 2 + 0: return launch_wave_nhwc_t<kBGR, 0>(reuse, p, grid, lds, s);
+    default: return launch_wave_nhwc_t<kBGR, 1>(reuse, p, grid, lds, s);
+    }
+}
+
 template <int FMT, int OUT>
 const void* wave_fn_t(int px, bool reuse) {
     switch (px * 2 + (reuse ? 1 : 0)) {
@@ -3291,11 +3436,11 @@ int resident_per_cu(const void* fn, int lds, int threads = kThreads) {
 // phase of every plane (luma / packed at bpp 1, 3, 4; NV12 chroma 2 (x >> 1); I420 chroma x >> 1).
 bool plan_wave(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
                const YTab* yt, uint32_t x0_mask, const Knobs& kn, WParams& w, int& px, bool& reuse, int& lds,
-               int& grid) {
+               int& grid, int only_px = 0) {
     const int npc = f == kI420 ? 2 : (f == kNV12 ? 1 : 0);
     const int lut = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
     const int budget = kn.wave_lds;
-    const int want_px = kn.px;
+    const int want_px = only_px ? only_px : kn.px;  // only_px: the interleaved variant exists for PX = 4 alone
     if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
     reuse = false;
     for (int Y = 0; Y + 1 < DH; Y++) {
@@ -3369,6 +3514,22 @@ const void* strip_fn(int f, int out, int pr, int px) {
     }
 }
 
+// The interleaved (NHWC, fp32) instantiations.
+template <int FMT, int PX>
+const void* strip_nhwc_fn_p(int pr) {
+    return pr ? (const void*)evam_pp_strip<FMT, 1, kStripD, PX, 1, true> : (const void*)evam_pp_strip<FMT, 1, kStripD, PX, 0, true>;
+}
+const void* strip_nhwc_fn(int f, int pr, int px) {
+    switch (f * 2 + (px == 2)) {
+    case kNV12 * 2: return strip_nhwc_fn_p<kNV12, 1>(pr);
+    case kNV12 * 2 + 1: return strip_nhwc_fn_p<kNV12, 2>(pr);
+    case kI420 * 2: return strip_nhwc_fn_p<kI420, 1>(pr);
+    case kI420 * 2 + 1: return strip_nhwc_fn_p<kI420, 2>(pr);
+    case kBGRX * 2: return strip_nhwc_fn_p<kBGRX, 1>(pr);
+    default: return strip_nhwc_fn_p<kBGRX, 2>(pr);
+    }
+}
+
 // Strip-kernel plan for a uniform 4:2:0 group (fills everything in TParams but the items, LUT, output
 // and colour fields).
 //  * Pixels per lane PX: 2 (128-column strips: one ~480-byte DMA segment per source row at 3.75x) where
@@ -3388,7 +3549,7 @@ const void* strip_fn(int f, int out, int pr, int px) {
 // REUSE path).
 bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
                 const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool pair_ok, TParams& p, int& pr, int& px, int& lds,
-                int& grid) {
+                int& grid, bool nhwc = false) {
     if (f != kNV12 && f != kI420 && f != kBGRX) return false;
     int shared = 0, vis = 0;
     for (int Y = 0; Y + 1 < DH; Y++) {
@@ -3432,7 +3593,8 @@ bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, 
     p.wave_bytes = kStripD * grp_bytes;
     lds = nw * p.wave_bytes + 16;  // dynamic LDS; + 16: a right-edge tap reads past its footprint (weight 0)
     if (lds + lut_static > 64 * 1024) return false;
-    const int res = std::max(1, std::min(wg_target, resident_per_cu(strip_fn(f, out_dtype, pr, px), lds)));
+    const void* const fn = nhwc ? strip_nhwc_fn(f, pr, px) : strip_fn(f, out_dtype, pr, px);
+    const int res = std::max(1, std::min(wg_target, resident_per_cu(fn, lds)));
     const int64_t slots = (int64_t)n_cu * res;
     const int64_t work = (int64_t)std::min(count, kArgItems) * p.tiles_x * DH;
     int th = (int)std::max<int64_t>(1, (work + slots - 1) / slots);
@@ -3482,6 +3644,25 @@ hipError_t launch_strip(int f, int out, int pr, int px, const TParams& p, dim3 g
     }
 }
 
+template <int FMT, int PX>
+hipError_t launch_strip_nhwc_t(int pr, const TParams& p, dim3 grid, int lds, hipStream_t s) {
+    const dim3 blk(64 * p.nw);
+    if (pr) hipLaunchKernelGGL((evam_pp_strip<FMT, 1, kStripD, PX, 1, true>), grid, blk, lds, s, p);
+    else hipLaunchKernelGGL((evam_pp_strip<FMT, 1, kStripD, PX, 0, true>), grid, blk, lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_strip_nhwc(int f, int pr, int px, const TParams& p, dim3 grid, int lds, hipStream_t s) {
+    switch (f * 2 + (px == 2)) {
+    case kNV12 * 2: return launch_strip_nhwc_t<kNV12, 1>(pr, p, grid, lds, s);
+    case kNV12 * 2 + 1: return launch_strip_nhwc_t<kNV12, 2>(pr, p, grid, lds, s);
+    case kI420 * 2: return launch_strip_nhwc_t<kI420, 1>(pr, p, grid, lds, s);
+    case kI420 * 2 + 1: return launch_strip_nhwc_t<kI420, 2>(pr, p, grid, lds, s);
+    case kBGRX * 2: return launch_strip_nhwc_t<kBGRX, 1>(pr, p, grid, lds, s);
+    default: return launch_strip_nhwc_t<kBGRX, 2>(pr, p, grid, lds, s);
+    }
+}
+
 // Band-kernel plan for a uniform 4:2:0 group whose consecutive output rows share source rows (vertical
 // upscales, C1). Fills the geometry, strips, bands and LDS fields of TParams (not items, LUT, output,
 // colour).
@@ -3494,7 +3675,8 @@ hipError_t launch_strip(int f, int out, int pr, int px, const TParams& p, dim3 g
 // Returns false for geometries it does not suit (fewer than 1 in 8 rows sharing source rows, footprints
 // over 1 KB, outputs wider than kMaxStrips strips).
 bool plan_band(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-               const YTab* yt, uint32_t x0_mask, const Knobs& kn, TParams& p, int& px, bool& dd, int& nw, int& lds) {
+               const YTab* yt, uint32_t x0_mask, const Knobs& kn, TParams& p, int& px, bool& dd, int& nw, int& lds,
+               int only_px = 0) {
     if (f != kNV12 && f != kI420) return false;
     int shared = 0, vis = 0;
     for (int Y = 0; Y + 1 < DH; Y++) {
@@ -3510,6 +3692,7 @@ bool plan_band(int f, const Geom& g, int DW, int DH, int count, int out_dtype, i
     px = 0;
     for (int cand : {4, 2, 1}) {
         if (kn.band_px > 0 && cand != kn.band_px) continue;
+        if (only_px && cand != only_px) continue;  // the interleaved variant exists for PX = 4 alone
         if (DW % cand) continue;
         wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, 64 * cand, mY, mC);
         if (mY <= 64 && mC <= 64) { px = cand; break; }
@@ -3584,6 +3767,16 @@ hipError_t launch_band(int f, int out, int px, bool dd, const TParams& p, dim3 g
     case kI420 * 2 + 0: return launch_band_t<kI420, 0>(px, dd, p, grid, nw, lds, s);
     default: return launch_band_t<kI420, 1>(px, dd, p, grid, nw, lds, s);
     }
+}
+
+// The interleaved (NHWC, u8, PX = 4) instantiations.
+hipError_t launch_band_nhwc(int f, bool dd, const TParams& p, dim3 grid, int nw, int lds, hipStream_t s) {
+    const dim3 blk(64 * nw);
+    if (f == kNV12 && dd) hipLaunchKernelGGL((evam_pp_band<kNV12, 0, 4, 1, true>), grid, blk, lds, s, p);
+    else if (f == kNV12) hipLaunchKernelGGL((evam_pp_band<kNV12, 0, 4, 0, true>), grid, blk, lds, s, p);
+    else if (dd) hipLaunchKernelGGL((evam_pp_band<kI420, 0, 4, 1, true>), grid, blk, lds, s, p);
+    else hipLaunchKernelGGL((evam_pp_band<kI420, 0, 4, 0, true>), grid, blk, lds, s, p);
+    return hipGetLastError();
 }
 
 template <int FMT, int OUT>
@@ -3780,6 +3973,10 @@ struct evam_pp {
     int memo_key[4] = {-1, -1, -1, -1};  // (format, staging buffer, row cap, DH) of memo_rg
     std::vector<uint32_t> memo_rg;       // per crop width: rows per group | groups of the whole height << 16
     TParams sc_tparams;            // strip-kernel arguments (3.5 KB: kept off the stack)
+    std::vector<XTab> sc_xt;       // interleaved output: the tables a group's kernel choice is planned on
+    std::vector<YTab> sc_yt;
+    int nhwc_key[4][16] = {};      // per format: what the last interleaved uniform group's choice depended on
+    int nhwc_ok[4] = {-1, -1, -1, -1};  // ... and the choice: 1 strip / wave kernel, 0 generic kernel (-1: none yet)
 };
 
 namespace {
@@ -3968,6 +4165,14 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     // The kernels address one output plane with 32-bit byte offsets.
     if (plane * esz > INT32_MAX)
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: dst plane %dx%d exceeds 2 GiB", DW, DH);
+    if (dst->layout != EVAM_LAYOUT_NCHW && dst->layout != EVAM_LAYOUT_NHWC)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: unknown dst layout %d", dst->layout);
+    const bool nhwc = dst->layout == EVAM_LAYOUT_NHWC;
+    // ... and one interleaved slot: its last element is at 3 * plane - 1.
+    if (nhwc && plane * 3 * esz > INT32_MAX)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: interleaved dst slot %dx%dx3 exceeds 2 GiB", DH, DW);
+    if (nhwc && ((uintptr_t)dst->data & (uintptr_t)(esz - 1)))
+        return fail(EVAM_PP_ERR_ALIGNMENT, "evam_pp_run: dst->data is not aligned to its %d-byte elements", esz);
     const Knobs& kn = h->knobs;
 
     // ---- validate sources ----
@@ -4103,6 +4308,65 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     //   per-item geometry       -> ROI kernel: raw ROI rect + source (RoiRec), geometry resolved on the device
     //   ROI plan impossible     -> generic kernel, per-item ItemDesc in the descriptor block
     enum { kPathNone, kPathUniform, kPathRoi, kPathGeneric };
+    // I420 paired chroma addresses both chroma planes from one buffer resource based at the lower one: for every
+    // item, the upper plane's offset from the lower plus its extent must fit the resource's 0x7FFFFFFF bytes (else
+    // no pairing for the group)
+    auto strip_pair_ok = [&](int f) {
+        bool ok = true;
+        if (f == kI420 && kn.strip_pair)
+            for (int m = 0; m < n_items && ok; m++) {
+                if (fmt[m] != f) continue;
+                const evam_image& sr = srcs[items ? items[m].src_index : m];
+                const int64_t d = (int64_t)((intptr_t)sr.planes[2] - (intptr_t)sr.planes[1]);
+                const int64_t ext = (int64_t)sr.pitch[d >= 0 ? 2 : 1] * (sr.height / 2);
+                ok = (d >= 0 ? d : -d) + ext <= (int64_t)0x7FFFFFFF;
+            }
+        return ok;
+    };
+    // Interleaved output takes the strip kernel in fp32 (12-byte stores, dword-aligned as the elements are) and the
+    // band (u8) and wave kernels' four-pixel stores where they are aligned to their width: DW % 4 == 0 makes every row and slot
+    // size a multiple of it, so the tensor's base decides (4 bytes for u8, 16 for fp32).
+    const bool nhwc_wave_ok = DW % 4 == 0 && ((uintptr_t)dst->data & (uintptr_t)(esz == 4 ? 15 : 3)) == 0;
+    // Does a strip or wave plan serve interleaved uniform group f? Decided here, ahead of the descriptor block, so
+    // that only a group the generic kernel serves puts its items' descriptors (which change with every set of
+    // frames) into it; the launch below plans again with the same arguments. Memoised on those arguments.
+    auto nhwc_uniform_ok = [&](int f) {
+        const int i = rep[f];
+        const evam_roi* r = items ? &items[i] : nullptr;
+        const evam_image& s = srcs[items ? r->src_index : i];
+        Geom& g = geo[i];
+        roi_geometry(f, s.width, s.height, r != nullptr, r ? r->x : 0, r ? r->y : 0, r ? r->w : 0, r ? r->h : 0,
+                     cfg->resize_mode, cfg->placement, DW, DH, g);
+        const bool pair_ok = strip_pair_ok(f);
+        const int key[16] = {1, g.cw, g.ch, g.rw, g.rh, g.ox, g.oy, DW, DH, cfg->out_dtype, count[f], (int)x0_mask[f],
+                             (int)nhwc_wave_ok, (int)pair_ok, g.x0 & 31, 0};
+        if (h->nhwc_ok[f] >= 0 && memcmp(key, h->nhwc_key[f], sizeof(key)) == 0) return h->nhwc_ok[f] == 1;
+        h->sc_xt.resize((size_t)DW);
+        h->sc_yt.resize((size_t)DH);
+        build_tables(g, DW, DH, h->tab_cache, h->sc_xt.data(), h->sc_yt.data());
+        bool ok = false;
+        int px = 0, lds = 0, grid = 0;
+        if (kn.strip && kn.wave != 2 && cfg->out_dtype == EVAM_DTYPE_F32) {
+            int pr = 0;
+            ok = plan_strip(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f],
+                            kn, pair_ok, h->sc_tparams, pr, px, lds, grid, true);
+        }
+        if (!ok && kn.band && kn.wave != 2 && kn.strip != 2 && cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok) {
+            int nw = 0;
+            bool dd = false;
+            ok = plan_band(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f], kn,
+                           h->sc_tparams, px, dd, nw, lds, 4);
+        }
+        if (!ok && kn.wave && nhwc_wave_ok) {
+            WParams w{};
+            bool reuse = false;
+            ok = plan_wave(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f], kn,
+                           w, px, reuse, lds, grid, 4);
+        }
+        memcpy(h->nhwc_key[f], key, sizeof(key));
+        h->nhwc_ok[f] = ok ? 1 : 0;
+        return ok;
+    };
     int path[4];
     QParams qp[4];
     int qlds[4] = {0, 0, 0, 0}, qbase[4] = {1, 1, 1, 1}, qrec[4] = {0, 0, 0, 0};
@@ -4111,7 +4375,10 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     for (int f = 0; f < 4; f++) {
         path[f] = kPathNone;
         if (!count[f]) continue;
-        if (uniform[f] && kn.rows) path[f] = kPathUniform;
+        // Interleaved output: uniform geometry tries the strip kernel (fp32 downscales) and the wave kernel (the rest,
+        // where its wide stores are aligned), see the launches below; the generic kernel serves everything else.
+        if (nhwc) path[f] = uniform[f] && kn.rows && nhwc_uniform_ok(f) ? kPathUniform : kPathGeneric;
+        else if (uniform[f] && kn.rows) path[f] = kPathUniform;
         else if (kn.roi && plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_cw[f]), count[f], h->n_cu,
                                     kn, qp[f], qbase[f], qlds[f], qslots[f])) path[f] = kPathRoi;
         else path[f] = kPathGeneric;
@@ -4443,24 +4710,13 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
             const XTab* xt_d = reinterpret_cast<const XTab*>(d_block + tab_off[f]);
             const YTab* yt_d = reinterpret_cast<const YTab*>(xt_d + DW);
             const int per_launch = std::min(count[f], kArgItems);
-            if (kn.strip && kn.wave != 2) {
+            if (kn.strip && kn.wave != 2 && (!nhwc || cfg->out_dtype == EVAM_DTYPE_F32)) {
                 TParams* tp = &h->sc_tparams;
                 int pr = 0, spx = 0, lds = 0, grid = 0;
                 const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
-                // I420 paired chroma addresses both chroma planes from one buffer resource based at the lower one:
-                // for every item, the upper plane's offset from the lower plus its extent must fit the resource's
-                // 0x7FFFFFFF bytes (else no pairing for the group)
-                bool pair_ok = true;
-                if (f == kI420 && kn.strip_pair)
-                    for (int m = mfirst[f]; m < mfirst[f + 1] && pair_ok; m++) {
-                        const int i = members[m];
-                        const evam_image& sr = srcs[items ? items[i].src_index : i];
-                        const int64_t d = (int64_t)((intptr_t)sr.planes[2] - (intptr_t)sr.planes[1]);
-                        const int64_t ext = (int64_t)sr.pitch[d >= 0 ? 2 : 1] * (sr.height / 2);
-                        pair_ok = (d >= 0 ? d : -d) + ext <= (int64_t)0x7FFFFFFF;
-                    }
+                const bool pair_ok = strip_pair_ok(f);
                 if (plan_strip(f, g0, DW, DH, count[f], cfg->out_dtype, h->n_cu, hx, reinterpret_cast<const YTab*>(hx + DW),
-                               x0_mask[f], kn, pair_ok, *tp, pr, spx, lds, grid)) {
+                               x0_mask[f], kn, pair_ok, *tp, pr, spx, lds, grid, nhwc)) {
                     tp->lut = lut_d;
                     tp->dst = dst->data;
                     tp->slot_offset = slot_offset;
@@ -4475,7 +4731,8 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                         // the strip pattern takes 1.7 us longer with each XCD on its own run of tiles,
                         // profiles/r03c_strip_bw.txt)
                         const dim3 gr((unsigned)tp->tiles_x, (unsigned)((DH + tp->TH - 1) / tp->TH), (unsigned)nm);
-                        hipError_t e = launch_strip(f, cfg->out_dtype, pr, spx, *tp, gr, lds, h->stream);
+                        hipError_t e = nhwc ? launch_strip_nhwc(f, pr, spx, *tp, gr, lds, h->stream)
+                                            : launch_strip(f, cfg->out_dtype, pr, spx, *tp, gr, lds, h->stream);
                         if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
                         launches++; kmask |= EVAM_KERNEL_STRIP;
                     }
@@ -4483,13 +4740,13 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                     continue;
                 }
             }
-            if (kn.band && kn.wave != 2 && kn.strip != 2) {
+            if (kn.band && kn.wave != 2 && kn.strip != 2 && (!nhwc || (cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok))) {
                 TParams* tp = &h->sc_tparams;
                 int bpx = 0, nw = 0, lds = 0;
                 bool dd = false;
                 const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
                 if (plan_band(f, g0, DW, DH, count[f], cfg->out_dtype, h->n_cu, hx, reinterpret_cast<const YTab*>(hx + DW),
-                              x0_mask[f], kn, *tp, bpx, dd, nw, lds)) {
+                              x0_mask[f], kn, *tp, bpx, dd, nw, lds, nhwc ? 4 : 0)) {
                     tp->lut = lut_d;
                     tp->dst = dst->data;
                     tp->slot_offset = slot_offset;
@@ -4503,14 +4760,15 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                         fill_args(tp->items, m0, nm);
                         tp->units = nm * tp->tiles_per_item;
                         const dim3 gr((unsigned)tp->tiles_x, (unsigned)((DH + tp->TH - 1) / tp->TH), (unsigned)nm);
-                        hipError_t e = launch_band(f, cfg->out_dtype, bpx, dd, *tp, gr, nw, lds, h->stream);
+                        hipError_t e = nhwc ? launch_band_nhwc(f, dd, *tp, gr, nw, lds, h->stream)
+                                            : launch_band(f, cfg->out_dtype, bpx, dd, *tp, gr, nw, lds, h->stream);
                         if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
                         launches++; kmask |= EVAM_KERNEL_BAND;
                     }
                     continue;
                 }
             }
-            if (kn.wave) {
+            if (kn.wave && (!nhwc || nhwc_wave_ok)) {
                 WParams w{};
                 int px = 0, lds = 0, grid = 0;
                 bool reuse = false;
@@ -4518,8 +4776,9 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                 // The wave kernel wins where consecutive output rows share source rows (vertical
                 // upscale: REUSE); for downscales the staged kernel's deeper shared staging is faster.
                 if (plan_wave(f, g0, DW, DH, count[f], cfg->out_dtype, h->n_cu, hx,
-                              reinterpret_cast<const YTab*>(hx + DW), x0_mask[f], kn, w, px, reuse, lds, grid) &&
-                    (reuse || kn.wave == 2)) {
+                              reinterpret_cast<const YTab*>(hx + DW), x0_mask[f], kn, w, px, reuse, lds, grid,
+                              nhwc ? 4 : 0) &&
+                    (reuse || kn.wave == 2 || nhwc)) {
                     w.ox = g0.ox;
                     w.rw = g0.rw;
                     w.lut = lut_d;
@@ -4533,13 +4792,15 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                     for (int m0 = mfirst[f]; m0 < mfirst[f + 1]; m0 += kArgItems) {
                         const int n = std::min(kArgItems, mfirst[f + 1] - m0);
                         fill_args(w.items, m0, n);
-                        hipError_t e = launch_wave(f, cfg->out_dtype, px, reuse, w, n * w.tiles_per_item, lds, h->stream);
+                        hipError_t e = nhwc ? launch_wave_nhwc(f, cfg->out_dtype, reuse, w, n * w.tiles_per_item, lds, h->stream)
+                                            : launch_wave(f, cfg->out_dtype, px, reuse, w, n * w.tiles_per_item, lds, h->stream);
                         if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
                         launches++; kmask |= EVAM_KERNEL_WAVE;
                     }
                     continue;
                 }
             }
+            if (!nhwc) {
             // Tile width: the widest of 256 / 128 columns whose staged row segment (the exact widest footprint of
             // any tile and crop origin of this group) fits the kernel's 1 KB slot.
             const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
@@ -4637,6 +4898,8 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                 launches++; kmask |= EVAM_KERNEL_ROWS;
             }
             continue;
+            }
+            return fail(EVAM_PP_ERR_HIP, "evam_pp_run: the interleaved group's plan did not repeat (internal error)");
         }
         const ItemDesc* items_d = reinterpret_cast<const ItemDesc*>(d_block + desc_off) + first[f];
         const TileCfg t = choose_tiles(DW, DH, cfg->out_dtype, kn);
@@ -4659,7 +4922,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         p.color_rgb = color_rgb;
         p.fill = fill;
         const int lds = t.lds;
-        if (lds > 64 * 1024) {
+        if (lds > 64 * 1024 && !nhwc) {
             hipError_t e = hipSuccess;
             switch (f * 2 + cfg->out_dtype) {
 #define SETATTR(F, O) case F * 2 + O: e = hipFuncSetAttribute((const void*)evam_pp_kernel<F, O>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); break;
@@ -4669,7 +4932,8 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
             }
             if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
-        hipError_t e = launch(f, cfg->out_dtype, p, (int)n_tiles, lds, h->stream);
+        hipError_t e = nhwc ? launch_nhwc(f, cfg->out_dtype, p, (int)n_tiles, lds, h->stream)
+                            : launch(f, cfg->out_dtype, p, (int)n_tiles, lds, h->stream);
         if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
         launches++; kmask |= EVAM_KERNEL_GENERIC;
     }

@@ -226,6 +226,7 @@ class InferenceModel:
     model_proc: dict | None = None
     out_dtype: str = "f32"
     name: str | None = None
+    layout: str = "nchw"  # "nhwc": the stage packs into a torch.channels_last blob, handed to ``fn`` unchanged
 
     def preproc_info(self, overrides: dict | None = None):
         from .preproc import PreProcInfo
@@ -893,7 +894,10 @@ class _InferenceStage:
 
         W, H = self.model.input_size
         dt = torch.float32 if self.model.out_dtype == "f32" else torch.uint8
-        return torch.empty((n, 3, H, W), dtype=dt, device=f"cuda:{self.device}")
+        if self.model.layout not in ("nchw", "nhwc"):
+            raise PreProcError(N.ERR_INVALID_ARG, f"model layout {self.model.layout!r} (nchw, nhwc)")
+        fmt = torch.channels_last if self.model.layout == "nhwc" else torch.contiguous_format
+        return torch.empty((n, 3, H, W), dtype=dt, device=f"cuda:{self.device}", memory_format=fmt)
 
 
 class DetectStage(_InferenceStage):
@@ -1272,6 +1276,8 @@ class Pipeline:
         self._runner = False
         self._out_backlog = collections.deque()  # runner mode: results a full destination queue could not take
         self._out_limit = 1  # held-back results at which the runner stops ingesting / running this stream
+        self._export_pp = None    # destination mode "publisher": this pipeline's handle for export_bgr
+        self._export_host = None  # ... and its pinned host buffer for a tick's packed BGR frames
         # logical device: pipeline k of the server runs on devices[(k - 1) mod G] (streams partitioned over GPUs)
         self.slot = server.slot_for(instance_id)
         self.device = server.devices[self.slot]
@@ -1394,8 +1400,41 @@ class Pipeline:
         dst = self.destination.get("metadata", self.destination)
         if dst.get("output") is None:
             return
-        for _, img, fr in items:
-            self._emit(fr, img)
+        frames = self._export_frames(items) if dst.get("mode") == "publisher" else itertools.repeat(None)
+        for (_, img, fr), frame in zip(items, frames):
+            self._emit(fr, img, frame)
+
+    def _export_frames(self, items):
+        """Destination mode ``"publisher"``: the packed H*W*3 BGR image (bytes) of every frame of ``items``, in
+        order. One ``export_bgr`` launch per run of equal-sized frames (a stream's frames share a size: one launch
+        per tick), one copy into this pipeline's pinned host buffer and one stream synchronisation per launch —
+        a synchronous copy per tick, accepted for this opt-in mode."""
+        import torch
+
+        if not items:
+            return []
+        if self._export_pp is None:
+            from . import preproc
+
+            self._export_pp = preproc.HipPreProcessor(device=self.device)
+        out, k = [], 0
+        while k < len(items):
+            w, h = items[k][1].width, items[k][1].height
+            e = k + 1
+            while e < len(items) and items[e][1].width == w and items[e][1].height == h:
+                e += 1
+            dev = self._export_pp.export_bgr([it[1] for it in items[k:e]])
+            total, each = dev.numel(), h * w * 3
+            if self._export_host is None or self._export_host.numel() < total:
+                self._export_host = torch.empty(total, dtype=torch.uint8, pin_memory=dev.is_cuda)
+            host = self._export_host[:total]
+            host.copy_(dev.reshape(-1), non_blocking=True)
+            if dev.is_cuda:
+                torch.cuda.current_stream(dev.device).synchronize()
+            raw = host.numpy()
+            out.extend(raw[i * each:(i + 1) * each].tobytes() for i in range(e - k))
+            k = e
+        return out
 
     def _fail(self, e):
         self.error = f"{type(e).__name__}: {e}"
@@ -1410,6 +1449,7 @@ class Pipeline:
             self.state = self.ABORTED if self._stop.is_set() else self.COMPLETED
         for st in self.stages:
             st.close()
+        self._close_export()
         self.end_time = time.time()
         dst = self.destination.get("metadata", self.destination)
         if dst.get("output") is not None:
@@ -1455,13 +1495,26 @@ class Pipeline:
                                    device=f"cuda:{self.device}")
         raise TypeError(f"unsupported frame object {type(item).__name__}")
 
-    def _emit(self, fr: P.FrameResult, img):
+    def _close_export(self):
+        if self._export_pp is not None:
+            self._export_pp.close()
+            self._export_pp = None
+        self._export_host = None
+
+    def _emit(self, fr: P.FrameResult, img, frame=None):
+        """One result to the destination: ``(img, fr)`` (mode ``"frames"``), the EVAM publisher's ``(meta, frame
+        bytes)`` (mode ``"publisher"``; ``frame`` from ``_export_frames``), else the gvametaconvert JSON line."""
         dst = self.destination.get("metadata", self.destination)
         out = dst.get("output")
         mode = dst.get("mode", "frames")
         if out is None:
             return
-        item = (img, fr) if mode == "frames" else P.gvametaconvert_json(fr)
+        if mode == "frames":
+            item = (img, fr)
+        elif mode == "publisher":
+            item = P.publisher_message(fr, frame)
+        else:
+            item = P.gvametaconvert_json(fr)
         if self._runner:
             self._put(out, item)
         else:
@@ -1519,6 +1572,7 @@ class Pipeline:
         finally:
             for s in self.stages:
                 s.close()
+            self._close_export()
             self.end_time = time.time()
             dst = self.destination.get("metadata", self.destination)
             if dst.get("output") is not None:
@@ -1527,8 +1581,11 @@ class Pipeline:
     def _flush(self, pend):
         for s in self.stages:
             s.process(pend)
-        for _, img, fr in pend:
-            self._emit(fr, img)
+        dst = self.destination.get("metadata", self.destination)
+        publish = dst.get("output") is not None and dst.get("mode") == "publisher"
+        frames = self._export_frames(pend) if publish else itertools.repeat(None)
+        for (_, img, fr), frame in zip(pend, frames):
+            self._emit(fr, img, frame)
 
     def stop(self):
         self._stop.set()

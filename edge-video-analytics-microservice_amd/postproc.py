@@ -18,6 +18,8 @@ from __future__ import annotations
 
 import json
 import math
+import random
+import string
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -221,3 +223,29 @@ def publisher_meta(fr: FrameResult, caps: str = "", img_handle: str = "") -> dic
         gva.append({"x": r.x, "y": r.y, "height": r.h, "width": r.w, "object_id": r.object_id, "tensor": tens})
     meta["gva_meta"] = gva
     return meta
+
+
+_HANDLE_ALPHABET = string.ascii_uppercase + string.digits
+
+
+def publisher_caps(width: int, height: int) -> str:
+    """The caps string of the packed BGR frame the EII templates' ``videoconvert ! video/x-raw,format=BGR !
+    appsink`` tail delivers (``eii/pipelines/object_detection/*/pipeline.json:6``)."""
+    return f"video/x-raw, format=(string)BGR, width=(int){int(width)}, height=(int){int(height)}"
+
+
+def image_handle(n: int = 10) -> str:
+    """A random handle of ``n`` characters ``A-Z0-9`` (``evas/publisher.py:95-103``)."""
+    return "".join(random.choices(_HANDLE_ALPHABET, k=n))
+
+
+def publisher_message(fr: FrameResult, frame, caps: str | None = None, img_handle: str | None = None) -> tuple:
+    """The ``(meta, frame)`` tuple the EVAM publisher sends with ``publish_frame`` set (``evas/publisher.py:
+    142-143,246-250``): ``publisher_meta`` plus the packed ``H*W*3`` BGR image of the frame (bytes, or any buffer;
+    ``HipPreProcessor.export_bgr`` produces it on the device). ``caps`` defaults to the BGR caps of the frame's
+    size, ``img_handle`` to a fresh 10-character handle."""
+    if caps is None:
+        caps = publisher_caps(fr.width, fr.height)
+    if img_handle is None:
+        img_handle = image_handle(10)
+    return publisher_meta(fr, caps, img_handle), frame

@@ -274,6 +274,23 @@ class Transforms(_SequenceABC):
                          x.resized_w, x.resized_h)
 
 
+def tensor_layout(out) -> int:
+    """``LAYOUT_NCHW`` or ``LAYOUT_NHWC`` of an ``[N,3,H,W]`` output tensor (``evam_tensor.layout``).
+
+    A contiguous tensor is planar, shapes where both formats coincide (H = W = 1) included; otherwise a tensor that
+    is contiguous in ``torch.channels_last`` is interleaved (DLS ``Convert(..., make_planar=false)``); anything
+    else raises ``ERR_INVALID_ARG``. Pure: reads only shape and strides, so it works on tensors of any device."""
+    import torch
+
+    if out.dim() == 4 and out.shape[1] == 3:
+        if out.is_contiguous():
+            return N.LAYOUT_NCHW
+        if out.is_contiguous(memory_format=torch.channels_last):
+            return N.LAYOUT_NHWC
+    raise PreProcError(N.ERR_INVALID_ARG, "out must be a contiguous or channels-last [N,3,H,W] tensor, got "
+                                          f"shape {tuple(out.shape)} strides {tuple(out.stride())}")
+
+
 class HipPreProcessor:
     """The ``pre-process-backend=hip`` implementation: one handle per (device, stream-thread)."""
 
@@ -298,6 +315,7 @@ class HipPreProcessor:
         self._last_cfg = None  # (info, dtype code, its fields, byref of the C struct) of the last call
         self._tdesc: dict = {}  # id(output tensor) -> (weakref, version, data_ptr, evam_tensor, dtype code, byref)
         self._default_info = PreProcInfo()
+        self._export_info: dict = {}  # color_space -> the PreProcInfo of export_bgr (identity resize, u8)
         self._run = self._lib.evam_pp_run
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         self._raw_stream = raw if raw is not None else (
@@ -355,8 +373,7 @@ class HipPreProcessor:
 
     def _tensor_entry(self, out):
         torch = self._torch
-        if out.dim() != 4 or out.shape[1] != 3 or not out.is_contiguous():
-            raise PreProcError(N.ERR_INVALID_ARG, f"out must be a contiguous [N,3,H,W] tensor, got {tuple(out.shape)}")
+        layout = tensor_layout(out)
         if out.dtype == torch.uint8:
             dt = N.DTYPE_U8
         elif out.dtype == torch.float32:
@@ -368,6 +385,7 @@ class HipPreProcessor:
         t = N.EvamTensor()
         t.data = out.data_ptr()
         t.n, t.c, t.h, t.w = (int(v) for v in out.shape)
+        t.layout = layout
         e = (weakref.ref(out), out._version, t.data, t, dt, ctypes.byref(t))
         if len(self._tdesc) >= 16:
             self._tdesc.clear()
@@ -433,6 +451,32 @@ class HipPreProcessor:
         if not want_transform:
             return None
         return Transforms(xf) if want_transform == "lazy" else list(Transforms(xf))
+
+    def export_bgr(self, srcs, out=None, color_space: str = "BGR"):
+        """The packed ``[N,H,W,3]`` uint8 image of every frame of ``srcs`` at source size, in one launch: the frame
+        the reference publishes (``videoconvert ! video/x-raw,format=BGR ! appsink``), with the BT.601 arithmetic of
+        the rest of this path. All frames must have one size. ``out``: an ``[N,H,W,3]`` uint8 device tensor to write
+        into (returned); default: a new one. Asynchronous, as :meth:`convert`."""
+        torch = self._torch
+        batch = srcs if isinstance(srcs, ImageBatch) else ImageBatch(srcs)
+        if len(batch) == 0:
+            raise PreProcError(N.ERR_INVALID_ARG, "export_bgr: no frames")
+        w, h = batch.images[0].width, batch.images[0].height
+        for im in batch.images:
+            if im.width != w or im.height != h:
+                raise PreProcError(N.ERR_INVALID_ARG, f"export_bgr: frames of one call must share a size, got "
+                                                      f"{w}x{h} and {im.width}x{im.height}")
+        shape = (len(batch), h, w, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise PreProcError(N.ERR_INVALID_ARG, f"export_bgr: out must be a contiguous uint8 {shape} tensor, got "
+                                                  f"{out.dtype} {tuple(out.shape)}")
+        info = self._export_info.get(color_space)
+        if info is None:
+            info = self._export_info[color_space] = PreProcInfo(resize="no-aspect-ratio", color_space=color_space)
+        self.convert(batch, out.permute(0, 3, 1, 2), info)
+        return out
 
 
 # Backend registry keyed by the DL Streamer element property value `pre-process-backend`.

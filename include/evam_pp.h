@@ -9,7 +9,9 @@
  *     -> aspect-ratio letterbox / central crop (DL Streamer model-proc "resize"/"crop")
  *     -> optional BGR->RGB                    (model-proc "color_space")
  *     -> optional range + mean/std to fp32    (model-proc "range"/"mean"/"std")
- *     -> planar NCHW write into batch slot n  (DL Streamer MatToMultiPlaneImage)
+ *     -> planar NCHW write into batch slot n  (DL Streamer MatToMultiPlaneImage), or, with
+ *        evam_tensor.layout = EVAM_LAYOUT_NHWC, the interleaved H x W x 3 image of that slot
+ *        (Convert(..., make_planar = false): channels-last model input, published BGR frames)
  *
  * Reference interface replaced (all paths relative to the reference tree):
  *   - element selection surface: pipelines/object_detection/vehicle/pipeline.json:5,13-18
@@ -37,7 +39,7 @@
 extern "C" {
 #endif
 
-#define EVAM_PP_ABI_VERSION 2 /* 2: evam_pp_run_slots */
+#define EVAM_PP_ABI_VERSION 3 /* 2: evam_pp_run_slots; 3: evam_tensor.layout (sizeof 32 -> 40) */
 
 /* DL Streamer FourCC values: fourcc(a,b,c,d) = a | b<<8 | c<<16 | d<<24. */
 enum evam_fourcc {
@@ -108,13 +110,24 @@ typedef struct evam_preproc {
     float std[3];          /* per OUTPUT channel                                                */
 } evam_preproc;
 
-/* Contiguous NCHW device tensor. Item i is written to slot  slot_offset + i * slot_stride.
- * (slot_stride = 16, slot_offset = t % 16 packs a [S,16,3,H,W] clip ring.) */
+/* Element order inside one output slot (DLS Convert's make_planar flag).
+ * NCHW: three planes of h*w elements, element (c, y, x) at c*h*w + y*w + x.
+ * NHWC: one interleaved image, element (y, x, c) at (y*w + x)*3 + c.
+ * c runs over the OUTPUT channel order either way: B,G,R, or R,G,B for EVAM_COLOR_RGB. */
+enum evam_layout { EVAM_LAYOUT_NCHW = 0, EVAM_LAYOUT_NHWC = 1 };
+
+/* Dense device tensor of n slots of 3*h*w elements. Item i is written to slot  slot_offset + i * slot_stride.
+ * (slot_stride = 16, slot_offset = t % 16 packs a [S,16,3,H,W] clip ring.)
+ * layout: evam_layout; a zero-initialised struct is planar. Any other value is EVAM_PP_ERR_INVALID_ARG.
+ * data needs the alignment of one element only (a u8 NHWC view may start at an odd address). With
+ * EVAM_LAYOUT_NHWC a slot's bytes (3*h*w*element size) must stay below 2 GiB. reserved is ignored. */
 typedef struct evam_tensor {
     void* data;
     int32_t n, c, h, w;
     int32_t slot_offset;
     int32_t slot_stride;
+    int32_t layout;
+    int32_t reserved;
 } evam_tensor;
 
 /* Per-item transform for post-processing (DLS ImageTransformationParams): a resized-image pixel
