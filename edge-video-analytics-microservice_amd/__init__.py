@@ -16,7 +16,7 @@ import sys as _sys
 
 from ._native import PreProcError, load_library  # noqa: F401
 from .preproc import (HipPreProcessor, Image, ImageBatch, PreProcInfo, Roi, RoiBatch, Transform,  # noqa: F401
-                      create_preprocessor, plane_layout, tensor_layout)
+                      create_preprocessor, output_dtype, plane_layout, tensor_layout)
 from . import _native as native  # noqa: F401
 from . import streams  # noqa: F401
 from . import postproc  # noqa: F401

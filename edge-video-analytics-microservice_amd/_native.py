@@ -43,7 +43,7 @@ STATUS_NAMES = {
 RESIZE_NO_ASPECT, RESIZE_ASPECT, RESIZE_ASPECT_CROP = 0, 1, 2
 PLACE_TOP_LEFT, PLACE_CENTER = 0, 1
 COLOR_BGR, COLOR_RGB = 0, 1
-DTYPE_U8, DTYPE_F32 = 0, 1
+DTYPE_U8, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3  # F16 / BF16: the F32 value rounded once (RNE)
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 NORM_RANGE, NORM_MEAN_STD = 1, 2
 OPT_STATS, OPT_TIMING = 1, 2
@@ -54,7 +54,7 @@ ABI_VERSION = 3  # 2: evam_pp_run_slots; 3: evam_tensor.layout
 EXPORTED_SYMBOLS = (
     "evam_pp_create", "evam_pp_run", "evam_pp_run_slots", "evam_pp_sync", "evam_pp_set_stream", "evam_pp_set_option",
     "evam_pp_get_stats", "evam_pp_destroy", "evam_pp_last_error", "evam_pp_abi_version",
-    "evam_pp_linear_table",
+    "evam_pp_linear_table", "evam_pp_norm_table",
 )
 
 c_i32 = ctypes.c_int32
@@ -129,6 +129,8 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_linear_table.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P(c_i32),
                                          P(ctypes.c_int16), P(ctypes.c_int16)]
     lib.evam_pp_linear_table.restype = ctypes.c_int
+    lib.evam_pp_norm_table.argtypes = [P(EvamPreproc), vp]
+    lib.evam_pp_norm_table.restype = ctypes.c_int
     return lib
 
 

@@ -19,7 +19,9 @@
 //         11-bit horizontal pass and the VResizeLinear 32s->8u vertical pass, maps the u8 result
 //         through the per-channel normalisation LUT (fp32 out) and stores planar NCHW, or, for a tensor with
 //         layout = EVAM_LAYOUT_NHWC, the slot's interleaved H x W x 3 image (a NHWC template parameter on the
-//         strip, band, wave and generic kernels: only the store epilogue differs).
+//         strip, band, wave and generic kernels: only the store epilogue differs). fp16 / bf16 output
+//         (EVAM_DTYPE_F16 / _BF16) is the same path with a table of 16-bit patterns and 2-byte stores (OUT = 2 on
+//         the generic, strip, ROI and wave kernels; interleaved 16-bit output: the generic kernel only).
 //  * Letterbox padding tiles never touch the source. Nothing is MFMA-shaped: the path is HBM-bound
 //    integer gather work (roofline: HBM, 8 TB/s).
 #include <hip/hip_runtime.h>
@@ -56,6 +58,14 @@ using namespace evam;
 constexpr int kThreads = 256;
 
 constexpr int kLutBytes = 3 * 256 * 4;
+// Output kind of a kernel instantiation (the OUT template parameter): 0 = u8, 1 = fp32 from the table, 2 = a 2-byte
+// element (fp16 or bf16: the same kernels, only the table's contents differ). The table section keeps 4-byte
+// entries for OUT = 2 with the 16-bit pattern in the low half, so vfinal's byte offsets, the LDS carve and
+// every kLutBytes term of the planners are those of fp32; the kernels read the low u16 of an entry.
+constexpr int out_kind(int out_dtype) {
+    return out_dtype == EVAM_DTYPE_U8 ? 0 : (out_dtype == EVAM_DTYPE_F32 ? 1 : 2);
+}
+constexpr int out_esz(int out) { return out == 1 ? 4 : (out == 2 ? 2 : 1); }
 // Stage-removal diagnostics (bits: 2 no pixel math, 4 no stores, 8 loads only, 16 no loads, 32/64/128 stop
 // early). Compile-time only: a product build is 0, every diagnostic branch folds away, and no environment
 // setting can change results. A build with -DEVAM_PP_ABLATE=bits computes INVALID tensors; evam_pp_create
@@ -217,18 +227,18 @@ __device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b) {
 __device__ __forceinline__ int vresize(uint32_t D0s, uint32_t D1s, uint32_t b0s, uint32_t b1s) {
     return (int)((mulhi_u24(b0s, D0s & 0xFFFF00u) + mulhi_u24(b1s, D1s & 0xFFFF00u) + 2u) >> 2);
 }
-// Same, for OUT == 1 returned as 4 * result (the byte offset into a float LUT section).
+// Same, for OUT != 0 returned as 4 * result (the byte offset into a LUT section of 4-byte entries).
 template <int OUT>
 __device__ __forceinline__ uint32_t vfinal(uint32_t D0s, uint32_t D1s, uint32_t b0s, uint32_t b1s) {
     const uint32_t x = mulhi_u24(b0s, D0s & 0xFFFF00u) + mulhi_u24(b1s, D1s & 0xFFFF00u) + 2u;
-    return OUT == 1 ? (x & ~3u) : (x >> 2);
+    return OUT != 0 ? (x & ~3u) : (x >> 2);
 }
 // Same, for horizontal results already masked with kVMask (a kernel that reuses a source row's results).
 constexpr uint32_t kVMask = 0xFFFF00u;
 template <int OUT>
 __device__ __forceinline__ uint32_t vfinal_masked(uint32_t D0m, uint32_t D1m, uint32_t b0s, uint32_t b1s) {
     const uint32_t x = mulhi_u24(b0s, D0m) + mulhi_u24(b1s, D1m) + 2u;
-    return OUT == 1 ? (x & ~3u) : (x >> 2);
+    return OUT != 0 ? (x & ~3u) : (x >> 2);
 }
 
 template <int FMT>
@@ -275,6 +285,10 @@ __device__ __forceinline__ void to_bgr(const uint32_t (&v)[3], int& b, int& g, i
 // offset, so every store is one saddr-form instruction with no 64-bit address arithmetic.
 // NHWC (interleaved output): d0 is the slot base and the pixel's three elements are adjacent at 3 * o
 // (d1, d2 unused); element stores only, so a slot may start at any element-aligned address.
+// OUT == 2: the 16-bit pattern in the low half of table entry i (fp16 / bf16 bits, no conversion on the device).
+__device__ __forceinline__ uint16_t lut_u16(const float* __restrict__ lut, int i) {
+    return *reinterpret_cast<const uint16_t*>(lut + i);
+}
 template <int OUT, bool NHWC = false>
 __device__ __forceinline__ void store_px(uint8_t* d0, uint8_t* d1, uint8_t* d2, const float* __restrict__ lut,
                                          uint32_t o, int v0, int v1, int v2) {
@@ -284,6 +298,11 @@ __device__ __forceinline__ void store_px(uint8_t* d0, uint8_t* d1, uint8_t* d2, 
             d0[o3] = (uint8_t)v0;
             d0[o3 + 1] = (uint8_t)v1;
             d0[o3 + 2] = (uint8_t)v2;
+        } else if constexpr (OUT == 2) {
+            uint16_t* const q = reinterpret_cast<uint16_t*>(d0 + (o3 << 1));
+            q[0] = lut_u16(lut, v0);
+            q[1] = lut_u16(lut, 256 + v1);
+            q[2] = lut_u16(lut, 512 + v2);
         } else {
             float* const q = reinterpret_cast<float*>(d0 + (o3 << 2));
             q[0] = lut[v0];
@@ -294,6 +313,11 @@ __device__ __forceinline__ void store_px(uint8_t* d0, uint8_t* d1, uint8_t* d2, 
         d0[o] = (uint8_t)v0;
         d1[o] = (uint8_t)v1;
         d2[o] = (uint8_t)v2;
+    } else if constexpr (OUT == 2) {
+        const uint32_t ob = o << 1;
+        *reinterpret_cast<uint16_t*>(d0 + ob) = lut_u16(lut, v0);
+        *reinterpret_cast<uint16_t*>(d1 + ob) = lut_u16(lut, 256 + v1);
+        *reinterpret_cast<uint16_t*>(d2 + ob) = lut_u16(lut, 512 + v2);
     } else {
         const uint32_t ob = o << 2;
         *reinterpret_cast<float*>(d0 + ob) = lut[v0];
@@ -331,13 +355,13 @@ __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
     const int X0 = tx * P.TW, Y0 = ty * P.TH;
     const int X1 = min(X0 + P.TW, P.DW), Y1 = min(Y0 + P.TH, P.DH);
     const size_t plane = (size_t)P.DW * P.DH;
-    const size_t esz = OUT == 1 ? 4 : 1;
+    const size_t esz = out_esz(OUT);
     uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)(P.slot_offset + it->index * P.slot_stride) * 3 * plane * esz;
     uint8_t* const d1 = d0 + plane * esz;
     uint8_t* const d2 = d1 + plane * esz;
 
     float* lut_s = reinterpret_cast<float*>(smem);
-    if constexpr (OUT == 1) {
+    if constexpr (OUT != 0) {
         for (int i = tid; i < 768; i += kThreads) lut_s[i] = P.lut[i];
     }
     ColEntry* coltab = reinterpret_cast<ColEntry*>(smem + P.offCol);
@@ -1205,8 +1229,8 @@ typedef int evam_v2i __attribute__((ext_vector_type(2)));
 typedef int evam_v3i __attribute__((ext_vector_type(3)));
 typedef int evam_v4i __attribute__((ext_vector_type(4)));
 
-// PX adjacent output pixels of one channel from one lane: a single buffer store of PX x 4 bytes (fp32)
-// or PX bytes (u8). lut == nullptr: u8 output.
+// PX adjacent output pixels of one channel from one lane: a single buffer store of PX x 4 bytes (fp32),
+// PX x 2 bytes (fp16 / bf16) or PX bytes (u8). lut == nullptr: u8 output.
 template <int OUT, int PX>
 __device__ __forceinline__ void store_vec(const __amdgpu_buffer_rsrc_t rs, uint32_t vo, int so, const float* lut,
                                           const int (&v)[PX]) {
@@ -1220,6 +1244,18 @@ __device__ __forceinline__ void store_vec(const __amdgpu_buffer_rsrc_t rs, uint3
             __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, so, EVAM_PP_STORE_AUX);
         } else {
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lut[v[0]]), rs, vo, so, EVAM_PP_STORE_AUX);
+        }
+    } else if constexpr (OUT == 2) {
+        // 2-byte elements: two table reads packed per dword (no conversion), one store of 2 PX bytes; the address is
+        // only 2-byte aligned (odd widths, odd slots), as the u8 path's dword stores are only byte aligned
+        auto P2 = [&](int a, int b) { return (int)((uint32_t)lut_u16(lut, a) | ((uint32_t)lut_u16(lut, b) << 16)); };
+        if constexpr (PX == 4) {
+            evam_v2i q = {P2(v[0], v[1]), P2(v[2], v[3])};
+            __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, so, EVAM_PP_STORE_AUX);
+        } else if constexpr (PX == 2) {
+            __builtin_amdgcn_raw_buffer_store_b32((uint32_t)P2(v[0], v[1]), rs, vo, so, EVAM_PP_STORE_AUX);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b16(lut_u16(lut, v[0]), rs, vo, so, EVAM_PP_STORE_AUX);
         }
     } else {
         if constexpr (PX == 4)
@@ -1247,6 +1283,17 @@ __device__ __forceinline__ void store_off(const __amdgpu_buffer_rsrc_t rs, uint3
             __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, 0, EVAM_PP_STORE_AUX);
         } else {
             __builtin_amdgcn_raw_buffer_store_b32((uint32_t)L(v[0]), rs, vo, 0, EVAM_PP_STORE_AUX);
+        }
+    } else if constexpr (OUT == 2) {
+        // the low u16 of each 4-byte entry, two per dword (see store_vec)
+        auto H = [&](uint32_t o) { return (uint32_t)*reinterpret_cast<const uint16_t*>(lb + o); };
+        if constexpr (PX == 4) {
+            evam_v2i q = {(int)(H(v[0]) | (H(v[1]) << 16)), (int)(H(v[2]) | (H(v[3]) << 16))};
+            __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, 0, EVAM_PP_STORE_AUX);
+        } else if constexpr (PX == 2) {
+            __builtin_amdgcn_raw_buffer_store_b32(H(v[0]) | (H(v[1]) << 16), rs, vo, 0, EVAM_PP_STORE_AUX);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)H(v[0]), rs, vo, 0, EVAM_PP_STORE_AUX);
         }
     } else {
         if constexpr (PX == 4)
@@ -1278,6 +1325,7 @@ __device__ __forceinline__ void store_off(const __amdgpu_buffer_rsrc_t rs, uint3
 template <int FMT, int OUT, int PX, bool REUSE, bool NHWC = false>
 __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
     static_assert(!NHWC || PX == 4, "the interleaved store is written for four pixels per lane");
+    static_assert(!NHWC || OUT != 2, "interleaved 2-byte output is served by the generic kernel");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     using T = FmtTraits<FMT>;
     constexpr bool kYUV = FMT == kNV12 || FMT == kI420;
@@ -1302,7 +1350,7 @@ __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
     const int pitch0 = it.pitch[0], pitch1 = it.pitch[1], pitch2 = it.pitch[2];
     const int x0 = it.x0, y0 = it.y0, ox = P.ox, rw = P.rw;
     const size_t plane = (size_t)P.DW * P.DH;
-    const size_t esz = OUT == 1 ? 4 : 1;
+    const size_t esz = out_esz(OUT);
     uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)(P.slot_offset + it.index * P.slot_stride) * 3 * plane * esz;
     uint8_t* const d1 = d0 + plane * esz;
     uint8_t* const d2 = d1 + plane * esz;
@@ -1492,7 +1540,7 @@ __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
         cur = plan(Yw0, pa, pb);
         issue(cur, wbuf);
     }
-    if constexpr (OUT == 1) {
+    if constexpr (OUT != 0) {
         for (int i = tid; i < 768; i += kThreads) lut_s[i] = P.lut[i];
         __syncthreads();  // every wave, including those without rows
     }
@@ -1730,7 +1778,7 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     static_assert(!NHWC || OUT == 1, "the interleaved strip store is fp32 only");
     constexpr int NS = NHWC ? 1 : 3;  // stores per pixel column group and row
     // the LUT at a static LDS address (folds into the reads' immediate offsets); the rings after it
-    __shared__ __attribute__((aligned(16))) float lut_s[OUT == 1 ? 768 : 4];
+    __shared__ __attribute__((aligned(16))) float lut_s[OUT != 0 ? 768 : 4];
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     static_assert(FMT == kNV12 || FMT == kI420 || FMT == kBGRX, "4:2:0 or BGRx sources");
     static_assert(D >= 1 && D <= 4, "ring depth");
@@ -1874,7 +1922,7 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     // follows the ring's DMA, so nothing makes the compiler drain the ring before the LUT barrier.
     const int nthr = p_nw * 64;
     const bool lut_early = nthr >= 256;
-    if constexpr (OUT == 1) {
+    if constexpr (OUT != 0) {
         if (lut_early && wave < 3) {
             const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void*)k_lut, (short)0, 3072, 0x00020000);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsL, (__attribute__((address_space(3))) void*)(lut_s + wave * 256), 16,
@@ -1892,7 +1940,7 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     bool xin[PX], padc[PX];
     uint32_t lY[PX], lC0[PX], lC1[PX], wp[PX], vo[PX];
     bool anyp = false;
-    const size_t esz = OUT == 1 ? 4 : 1;
+    const size_t esz = out_esz(OUT);
 #pragma unroll
     for (int j = 0; j < PX; j++) {
         const int X = X0 + lane + 64 * j;
@@ -1934,10 +1982,10 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     const __amdgpu_buffer_rsrc_t rsO2 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d0 : d2), (short)0, 0x7FFFFFFF, 0x00020000);
     // fill in source channel order (P.fill is in output plane order)
     const uint32_t fq0 = P.fill & 0xFF, fq1 = (P.fill >> 8) & 0xFF, fq2 = (P.fill >> 16) & 0xFF;
-    const uint32_t fsh = OUT == 1 ? 2 : 0;
+    const uint32_t fsh = OUT != 0 ? 2 : 0;
     const uint32_t fill0 = (k_rgb ? fq2 : fq0) << fsh, fill1 = fq1 << fsh, fill2 = (k_rgb ? fq0 : fq2) << fsh;
 
-    if constexpr (OUT == 1) {
+    if constexpr (OUT != 0) {
         if (lut_early) {
             // this wave's LUT section landed once at most the ring's DMA instructions are outstanding; the
             // barrier then needs no vmcnt(0): each wave waits for its own ring rows in the loop
@@ -2001,6 +2049,11 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
             __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + v0), rsO0, vo[j], so, EVAM_PP_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + 1024 + v1), rsO1, vo[j], so, EVAM_PP_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + 2048 + v2), rsO2, vo[j], so, EVAM_PP_STORE_AUX);
+        } else if constexpr (OUT == 2) {
+            // the low u16 of the entry: lane l holds columns l, l + 64, so a store instruction covers 128 contiguous bytes
+            __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const uint16_t*>(lutb + v0), rsO0, vo[j], so, EVAM_PP_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const uint16_t*>(lutb + 1024 + v1), rsO1, vo[j], so, EVAM_PP_STORE_AUX);
+            __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const uint16_t*>(lutb + 2048 + v2), rsO2, vo[j], so, EVAM_PP_STORE_AUX);
         } else {
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v0, rsO0, vo[j], so, EVAM_PP_STORE_AUX);
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v1, rsO1, vo[j], so, EVAM_PP_STORE_AUX);
@@ -2715,7 +2768,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
     // Sections in source channel order (B, G, R): RGB output swaps the B / R output planes instead of the
     // values (see rsD0 / rsD2), so the per-pixel path carries no swap.
     float* lut_s = reinterpret_cast<float*>(smem);
-    if constexpr (OUT == 1) {
+    if constexpr (OUT != 0) {
         const int c0 = wave * 48, c = c0 + lane, sec = c >> 6;  // 192 chunks of 16 B: 48 per wave
         const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void*)P.lut, (short)0, 3072, 0x00020000);
         if (lane < 48)
@@ -2750,7 +2803,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
     if ((kAblate & 64) && rw != -7) return;
     const double scx = 1. / ((double)rw / cw), scy = 1. / ((double)rh / ch);
     const size_t plane = (size_t)P.DW * P.DH;
-    const size_t esz = OUT == 1 ? 4 : 1;
+    const size_t esz = out_esz(OUT);
     const int slot = P.slot_offset + item * P.slot_stride;
     uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)slot * 3 * plane * esz;
     uint8_t* const d1 = d0 + plane * esz;
@@ -2877,7 +2930,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
     lds_barrier();  // column table visible to the per-lane setup; group 0's DMA stays in flight
     EVAM_STAMP(9);
     // fill in source channel order (P.fill is in output plane order); fp32: LUT byte offsets
-    const uint32_t fsh = OUT == 1 ? 2 : 0;
+    const uint32_t fsh = OUT != 0 ? 2 : 0;
     const uint32_t fq0 = P.fill & 0xFF, fq1 = (P.fill >> 8) & 0xFF, fq2 = (P.fill >> 16) & 0xFF;
     const uint32_t f0 = (P.color_rgb ? fq2 : fq0) << fsh, f1 = fq1 << fsh, f2 = (P.color_rgb ? fq0 : fq2) << fsh;
     // Per-lane state for quad steps k < K, identical for every group: row of the quad inside the
@@ -3068,6 +3121,47 @@ void build_lut(const evam_preproc& cfg, float* lut) {
         }
 }
 
+// fp32 bits -> fp16 bits, round to nearest even, in integer arithmetic: subnormals, overflow to +-inf, NaN stays
+// (quiet) NaN, the sign of zero is kept.
+uint16_t f32_to_f16_bits(uint32_t x) {
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));
+    if (a >= 0x38800000u) {  // >= 2^-14: a normal fp16, or past its range
+        const uint32_t r = a - 0x38000000u;  // exponent bias 127 -> 15
+        const uint32_t q = (r + 0xFFFu + ((r >> 13) & 1u)) >> 13;  // a mantissa carry moves into the exponent
+        return (uint16_t)(sign | std::min(q, 0x7C00u));
+    }
+    const uint32_t e = a >> 23;
+    if (e < 102) return (uint16_t)sign;  // < 2^-25: below half of the smallest subnormal
+    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, sh = 126 - e;  // value = m * 2^-sh units of 2^-24, sh in 14..24
+    uint32_t q = m >> sh;
+    const uint32_t rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    if (rem > half || (rem == half && (q & 1u))) q++;  // q == 0x400: the smallest normal
+    return (uint16_t)(sign | q);
+}
+// fp32 bits -> bf16 bits, round to nearest even.
+uint16_t f32_to_bf16_bits(uint32_t x) {
+    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((x >> 16) | 0x40u);
+    return (uint16_t)((x + 0x7FFFu + ((x >> 16) & 1u)) >> 16);
+}
+
+// The 768 table elements [c][u] in cfg.out_dtype: build_lut's fp32 value, narrowed once for the 16-bit types.
+// `out`: 768 floats (F32) or 768 u16 (F16 / BF16). The caller validated out_dtype and std.
+void norm_table(const evam_preproc& cfg, void* out) {
+    if (cfg.out_dtype == EVAM_DTYPE_F32) {
+        build_lut(cfg, static_cast<float*>(out));
+        return;
+    }
+    float f[768];
+    build_lut(cfg, f);
+    uint16_t* o = static_cast<uint16_t*>(out);
+    for (int i = 0; i < 768; i++) {
+        uint32_t b;
+        memcpy(&b, &f[i], 4);
+        o[i] = cfg.out_dtype == EVAM_DTYPE_F16 ? f32_to_f16_bits(b) : f32_to_bf16_bits(b);
+    }
+}
+
 
 struct TileCfg {
     int TW, TH, offCol, offRow, lds;
@@ -3139,7 +3233,7 @@ TileCfg choose_tiles(int DW, int DH, int out_dtype, const Knobs& k) {
     t.TH = std::max(1, std::min(DH, 4096 / t.TW));
     if (k.tw > 0) t.TW = std::max(1, std::min(DW, k.tw));
     if (k.th > 0) t.TH = std::max(1, std::min(DH, k.th));
-    t.offCol = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
+    t.offCol = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
     t.offRow = t.offCol + (int)sizeof(ColEntry) * t.TW;
     t.lds = t.offRow + (int)sizeof(RowEntry) * t.TH;
     return t;
@@ -3278,6 +3372,13 @@ hipError_t launch_nhwc_t(const KParams& p, int grid, int lds, hipStream_t s) {
 }
 
 hipError_t launch(int f, int out, const KParams& p, int grid, int lds, hipStream_t s) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f) {
+        case kNV12: return launch_t<kNV12, 2>(p, grid, lds, s);
+        case kI420: return launch_t<kI420, 2>(p, grid, lds, s);
+        case kBGRX: return launch_t<kBGRX, 2>(p, grid, lds, s);
+        default: return launch_t<kBGR, 2>(p, grid, lds, s);
+        }
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return launch_t<kNV12, 0>(p, grid, lds, s);
     case kNV12 * 2 + 1: return launch_t<kNV12, 1>(p, grid, lds, s);
@@ -3291,6 +3392,13 @@ hipError_t launch(int f, int out, const KParams& p, int grid, int lds, hipStream
 }
 
 hipError_t launch_nhwc(int f, int out, const KParams& p, int grid, int lds, hipStream_t s) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f) {
+        case kNV12: return launch_nhwc_t<kNV12, 2>(p, grid, lds, s);
+        case kI420: return launch_nhwc_t<kI420, 2>(p, grid, lds, s);
+        case kBGRX: return launch_nhwc_t<kBGRX, 2>(p, grid, lds, s);
+        default: return launch_nhwc_t<kBGR, 2>(p, grid, lds, s);
+        }
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return launch_nhwc_t<kNV12, 0>(p, grid, lds, s);
     case kNV12 * 2 + 1: return launch_nhwc_t<kNV12, 1>(p, grid, lds, s);
@@ -3326,6 +3434,13 @@ hipError_t launch_roi_t(int px, int nb, const QParams& p, int grid, int lds, hip
 }
 
 hipError_t launch_roi(int f, int out, int px, int nb, const QParams& p, int grid, int lds, hipStream_t s) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f) {
+        case kNV12: return launch_roi_t<kNV12, 2>(px, nb, p, grid, lds, s);
+        case kI420: return launch_roi_t<kI420, 2>(px, nb, p, grid, lds, s);
+        case kBGRX: return launch_roi_t<kBGRX, 2>(px, nb, p, grid, lds, s);
+        default: return launch_roi_t<kBGR, 2>(px, nb, p, grid, lds, s);
+        }
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return launch_roi_t<kNV12, 0>(px, nb, p, grid, lds, s);
     case kNV12 * 2 + 1: return launch_roi_t<kNV12, 1>(px, nb, p, grid, lds, s);
@@ -3355,6 +3470,13 @@ hipError_t launch_wave_p(int px, bool reuse, const WParams& p, int grid, int lds
 }
 
 hipError_t launch_wave(int f, int out, int px, bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f) {
+        case kNV12: return launch_wave_p<kNV12, 2>(px, reuse, p, grid, lds, s);
+        case kI420: return launch_wave_p<kI420, 2>(px, reuse, p, grid, lds, s);
+        case kBGRX: return launch_wave_p<kBGRX, 2>(px, reuse, p, grid, lds, s);
+        default: return launch_wave_p<kBGR, 2>(px, reuse, p, grid, lds, s);
+        }
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return launch_wave_p<kNV12, 0>(px, reuse, p, grid, lds, s);
     case kNV12 * 2 + 1: return launch_wave_p<kNV12, 1>(px, reuse, p, grid, lds, s);
@@ -3400,6 +3522,13 @@ const void* wave_fn_t(int px, bool reuse) {
     }
 }
 const void* wave_fn(int f, int out, int px, bool reuse) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f) {
+        case kNV12: return wave_fn_t<kNV12, 2>(px, reuse);
+        case kI420: return wave_fn_t<kI420, 2>(px, reuse);
+        case kBGRX: return wave_fn_t<kBGRX, 2>(px, reuse);
+        default: return wave_fn_t<kBGR, 2>(px, reuse);
+        }
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return wave_fn_t<kNV12, 0>(px, reuse);
     case kNV12 * 2 + 1: return wave_fn_t<kNV12, 1>(px, reuse);
@@ -3438,7 +3567,7 @@ bool plan_wave(int f, const Geom& g, int DW, int DH, int count, int out_dtype, i
                const YTab* yt, uint32_t x0_mask, const Knobs& kn, WParams& w, int& px, bool& reuse, int& lds,
                int& grid, int only_px = 0) {
     const int npc = f == kI420 ? 2 : (f == kNV12 ? 1 : 0);
-    const int lut = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
+    const int lut = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
     const int budget = kn.wave_lds;
     const int want_px = only_px ? only_px : kn.px;  // only_px: the interleaved variant exists for PX = 4 alone
     if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
@@ -3498,6 +3627,15 @@ const void* strip_fn_p(int pr) {
     return pr ? (const void*)evam_pp_strip<FMT, OUT, kStripD, PX, 1> : (const void*)evam_pp_strip<FMT, OUT, kStripD, PX, 0>;
 }
 const void* strip_fn(int f, int out, int pr, int px) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f * 2 + (px == 2)) {
+        case kNV12 * 2: return strip_fn_p<kNV12, 2, 1>(pr);
+        case kNV12 * 2 + 1: return strip_fn_p<kNV12, 2, 2>(pr);
+        case kI420 * 2: return strip_fn_p<kI420, 2, 1>(pr);
+        case kI420 * 2 + 1: return strip_fn_p<kI420, 2, 2>(pr);
+        case kBGRX * 2: return strip_fn_p<kBGRX, 2, 1>(pr);
+        default: return strip_fn_p<kBGRX, 2, 2>(pr);
+        }
     switch ((f * 2 + out) * 2 + (px == 2)) {
     case (kNV12 * 2 + 0) * 2: return strip_fn_p<kNV12, 0, 1>(pr);
     case (kNV12 * 2 + 0) * 2 + 1: return strip_fn_p<kNV12, 0, 2>(pr);
@@ -3588,7 +3726,7 @@ bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, 
     if (kn.strip_nw > 0) nw = std::min(8, kn.strip_nw);
     p.nw = nw;
     p.tiles_x = (nstrips + nw - 1) / nw;
-    const int lut_static = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 16;  // the kernel's static LDS
+    const int lut_static = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 16;  // the kernel's static LDS
     const int wg_target = std::max(1, std::min(32, kn.strip_waves) / nw);
     p.wave_bytes = kStripD * grp_bytes;
     lds = nw * p.wave_bytes + 16;  // dynamic LDS; + 16: a right-edge tap reads past its footprint (weight 0)
@@ -3628,6 +3766,15 @@ hipError_t launch_strip_t(int pr, const TParams& p, dim3 grid, int lds, hipStrea
 }
 
 hipError_t launch_strip(int f, int out, int pr, int px, const TParams& p, dim3 grid, int lds, hipStream_t s) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f * 2 + (px == 2)) {
+        case kNV12 * 2: return launch_strip_t<kNV12, 2, 1>(pr, p, grid, lds, s);
+        case kNV12 * 2 + 1: return launch_strip_t<kNV12, 2, 2>(pr, p, grid, lds, s);
+        case kI420 * 2: return launch_strip_t<kI420, 2, 1>(pr, p, grid, lds, s);
+        case kI420 * 2 + 1: return launch_strip_t<kI420, 2, 2>(pr, p, grid, lds, s);
+        case kBGRX * 2: return launch_strip_t<kBGRX, 2, 1>(pr, p, grid, lds, s);
+        default: return launch_strip_t<kBGRX, 2, 2>(pr, p, grid, lds, s);
+        }
     switch ((f * 2 + out) * 2 + (px == 2)) {
     case (kNV12 * 2 + 0) * 2: return launch_strip_t<kNV12, 0, 1>(pr, p, grid, lds, s);
     case (kNV12 * 2 + 0) * 2 + 1: return launch_strip_t<kNV12, 0, 2>(pr, p, grid, lds, s);
@@ -3786,6 +3933,13 @@ const void* roi_fn_t(int px, int nb) {
          : px == 2 ? (const void*)evam_pp_roi<FMT, OUT, 2, 2> : (const void*)evam_pp_roi<FMT, OUT, 1, 2>;
 }
 const void* roi_fn(int f, int out, int px, int nb) {
+    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
+        switch (f) {
+        case kNV12: return roi_fn_t<kNV12, 2>(px, nb);
+        case kI420: return roi_fn_t<kI420, 2>(px, nb);
+        case kBGRX: return roi_fn_t<kBGRX, 2>(px, nb);
+        default: return roi_fn_t<kBGR, 2>(px, nb);
+        }
     switch (f * 2 + out) {
     case kNV12 * 2 + 0: return roi_fn_t<kNV12, 0>(px, nb);
     case kNV12 * 2 + 1: return roi_fn_t<kNV12, 1>(px, nb);
@@ -3818,7 +3972,7 @@ bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, i
     q.TH = (int64_t)DW * DH <= 32768 ? DH : std::max(8, std::min(DH, 16384 / DW));
     if (kn.roi_th > 0) q.TH = std::max(1, std::min(DH, kn.roi_th));
     base_tiles = (DH + q.TH - 1) / q.TH;
-    q.offXT = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
+    q.offXT = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
     q.offYT = q.offXT + (int)sizeof(XTab) * DW;
     q.offBuf = q.offYT + (int)sizeof(YTab) * q.TH;
     const int64_t grid = (int64_t)count * base_tiles;
@@ -4132,6 +4286,19 @@ int evam_pp_linear_table(int src_size, int dst_size, int is_x, int32_t* ofs, int
     return EVAM_PP_OK;
 }
 
+int evam_pp_norm_table(const evam_preproc* cfg, void* out) {
+    if (!cfg || !out) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_norm_table: NULL argument");
+    if (cfg->out_dtype == EVAM_DTYPE_U8)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_norm_table: u8 output has no normalisation table");
+    if (cfg->out_dtype != EVAM_DTYPE_F32 && cfg->out_dtype != EVAM_DTYPE_F16 && cfg->out_dtype != EVAM_DTYPE_BF16)
+        return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_norm_table: unknown out_dtype %d", cfg->out_dtype);
+    if (cfg->norm_flags & EVAM_NORM_MEAN_STD)
+        for (int c = 0; c < 3; c++)
+            if (cfg->std[c] == 0.f) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_norm_table: std[%d] == 0", c);
+    norm_table(*cfg, out);
+    return EVAM_PP_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -4150,18 +4317,20 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     if (dst->c != 3) return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_run: dst must have 3 channels (got %d)", dst->c);
     if (dst->n <= 0 || dst->h <= 0 || dst->w <= 0)
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: bad dst shape %dx%dx%dx%d", dst->n, dst->c, dst->h, dst->w);
-    if (cfg->out_dtype != EVAM_DTYPE_U8 && cfg->out_dtype != EVAM_DTYPE_F32)
+    if (cfg->out_dtype != EVAM_DTYPE_U8 && cfg->out_dtype != EVAM_DTYPE_F32 && cfg->out_dtype != EVAM_DTYPE_F16 &&
+        cfg->out_dtype != EVAM_DTYPE_BF16)
         return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_run: unknown out_dtype %d", cfg->out_dtype);
+    const bool half = cfg->out_dtype == EVAM_DTYPE_F16 || cfg->out_dtype == EVAM_DTYPE_BF16;  // 2-byte elements
     if (cfg->resize_mode < 0 || cfg->resize_mode > 2)
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: unknown resize_mode %d", cfg->resize_mode);
-    if ((cfg->norm_flags & EVAM_NORM_MEAN_STD) && cfg->out_dtype == EVAM_DTYPE_F32)
+    if ((cfg->norm_flags & EVAM_NORM_MEAN_STD) && cfg->out_dtype != EVAM_DTYPE_U8)
         for (int c = 0; c < 3; c++)
             if (cfg->std[c] == 0.f) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: std[%d] == 0", c);
     const int DW = dst->w, DH = dst->h;
     const int64_t plane = (int64_t)DW * DH;
     if (plane * 3 * (int64_t)dst->n > ((int64_t)1 << 40))
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: dst too large");
-    const int esz = cfg->out_dtype == EVAM_DTYPE_F32 ? 4 : 1;
+    const int esz = out_esz(out_kind(cfg->out_dtype));
     // The kernels address one output plane with 32-bit byte offsets.
     if (plane * esz > INT32_MAX)
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: dst plane %dx%d exceeds 2 GiB", DW, DH);
@@ -4330,7 +4499,10 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     // Does a strip or wave plan serve interleaved uniform group f? Decided here, ahead of the descriptor block, so
     // that only a group the generic kernel serves puts its items' descriptors (which change with every set of
     // frames) into it; the launch below plans again with the same arguments. Memoised on those arguments.
-    auto nhwc_uniform_ok = [&](int f) {
+    // The same question for a planar 16-bit group: the strip kernel, or the wave kernel where rows share source rows;
+    // where fp32 would fall to the staged or row kernels (not instantiated for 2-byte elements) the generic kernel
+    // serves the group, which needs its descriptors in the block too.
+    auto planned_uniform_ok = [&](int f) {
         const int i = rep[f];
         const evam_roi* r = items ? &items[i] : nullptr;
         const evam_image& s = srcs[items ? r->src_index : i];
@@ -4339,29 +4511,30 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                      cfg->resize_mode, cfg->placement, DW, DH, g);
         const bool pair_ok = strip_pair_ok(f);
         const int key[16] = {1, g.cw, g.ch, g.rw, g.rh, g.ox, g.oy, DW, DH, cfg->out_dtype, count[f], (int)x0_mask[f],
-                             (int)nhwc_wave_ok, (int)pair_ok, g.x0 & 31, 0};
+                             (int)nhwc_wave_ok, (int)pair_ok, g.x0 & 31, (int)nhwc};
         if (h->nhwc_ok[f] >= 0 && memcmp(key, h->nhwc_key[f], sizeof(key)) == 0) return h->nhwc_ok[f] == 1;
         h->sc_xt.resize((size_t)DW);
         h->sc_yt.resize((size_t)DH);
         build_tables(g, DW, DH, h->tab_cache, h->sc_xt.data(), h->sc_yt.data());
         bool ok = false;
         int px = 0, lds = 0, grid = 0;
-        if (kn.strip && kn.wave != 2 && cfg->out_dtype == EVAM_DTYPE_F32) {
+        if (kn.strip && kn.wave != 2 && (cfg->out_dtype == EVAM_DTYPE_F32 || !nhwc)) {
             int pr = 0;
             ok = plan_strip(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f],
-                            kn, pair_ok, h->sc_tparams, pr, px, lds, grid, true);
+                            kn, pair_ok, h->sc_tparams, pr, px, lds, grid, nhwc);
         }
-        if (!ok && kn.band && kn.wave != 2 && kn.strip != 2 && cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok) {
+        if (!ok && nhwc && kn.band && kn.wave != 2 && kn.strip != 2 && cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok) {
             int nw = 0;
             bool dd = false;
             ok = plan_band(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f], kn,
                            h->sc_tparams, px, dd, nw, lds, 4);
         }
-        if (!ok && kn.wave && nhwc_wave_ok) {
+        if (!ok && kn.wave && (!nhwc || nhwc_wave_ok)) {
             WParams w{};
             bool reuse = false;
             ok = plan_wave(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f], kn,
-                           w, px, reuse, lds, grid, 4);
+                           w, px, reuse, lds, grid, nhwc ? 4 : 0) &&
+                 (reuse || kn.wave == 2 || nhwc);
         }
         memcpy(h->nhwc_key[f], key, sizeof(key));
         h->nhwc_ok[f] = ok ? 1 : 0;
@@ -4377,7 +4550,9 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         if (!count[f]) continue;
         // Interleaved output: uniform geometry tries the strip kernel (fp32 downscales) and the wave kernel (the rest,
         // where its wide stores are aligned), see the launches below; the generic kernel serves everything else.
-        if (nhwc) path[f] = uniform[f] && kn.rows && nhwc_uniform_ok(f) ? kPathUniform : kPathGeneric;
+        // 16-bit output: interleaved is the generic kernel's; planar uniform groups take the strip or wave kernel.
+        if (nhwc) path[f] = !half && uniform[f] && kn.rows && planned_uniform_ok(f) ? kPathUniform : kPathGeneric;
+        else if (half && uniform[f] && kn.rows) path[f] = planned_uniform_ok(f) ? kPathUniform : kPathGeneric;
         else if (uniform[f] && kn.rows) path[f] = kPathUniform;
         else if (kn.roi && plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_cw[f]), count[f], h->n_cu,
                                     kn, qp[f], qbase[f], qlds[f], qslots[f])) path[f] = kPathRoi;
@@ -4440,8 +4615,8 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     }
     h->h_block.resize(nbytes);
     uint8_t* blk = h->h_block.data();
-    if (cfg->out_dtype == EVAM_DTYPE_F32) {
-        // The LUT depends only on the normalisation fields: rebuilt when they change.
+    if (cfg->out_dtype != EVAM_DTYPE_U8) {
+        // The LUT depends only on the dtype and the normalisation fields: rebuilt when they change.
         evam_preproc key{};
         key.out_dtype = cfg->out_dtype;
         key.norm_flags = cfg->norm_flags;
@@ -4449,7 +4624,17 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         memcpy(key.mean, cfg->mean, sizeof(key.mean));
         memcpy(key.std, cfg->std, sizeof(key.std));
         if (!h->lut_valid || memcmp(&key, &h->lut_key, sizeof(key)) != 0) {
-            build_lut(*cfg, h->lut);
+            if (half) {
+                // norm_table's 16-bit elements, one per 4-byte entry (low half; the kernels read only that)
+                uint16_t t16[768];
+                norm_table(*cfg, t16);
+                for (int i = 0; i < 768; i++) {
+                    const uint32_t b = t16[i];
+                    memcpy(&h->lut[i], &b, 4);
+                }
+            } else {
+                norm_table(*cfg, h->lut);
+            }
             h->lut_key = key;
             h->lut_valid = true;
         }
@@ -4740,7 +4925,8 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                     continue;
                 }
             }
-            if (kn.band && kn.wave != 2 && kn.strip != 2 && (!nhwc || (cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok))) {
+            if (kn.band && kn.wave != 2 && kn.strip != 2 && !half &&
+                (!nhwc || (cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok))) {
                 TParams* tp = &h->sc_tparams;
                 int bpx = 0, nw = 0, lds = 0;
                 bool dd = false;
@@ -4800,7 +4986,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
                     continue;
                 }
             }
-            if (!nhwc) {
+            if (!nhwc && !half) {
             // Tile width: the widest of 256 / 128 columns whose staged row segment (the exact widest footprint of
             // any tile and crop origin of this group) fits the kernel's 1 KB slot.
             const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
@@ -4899,7 +5085,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
             }
             continue;
             }
-            return fail(EVAM_PP_ERR_HIP, "evam_pp_run: the interleaved group's plan did not repeat (internal error)");
+            return fail(EVAM_PP_ERR_HIP, "evam_pp_run: the interleaved or 16-bit group's plan did not repeat (internal error)");
         }
         const ItemDesc* items_d = reinterpret_cast<const ItemDesc*>(d_block + desc_off) + first[f];
         const TileCfg t = choose_tiles(DW, DH, cfg->out_dtype, kn);
@@ -4924,10 +5110,11 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         const int lds = t.lds;
         if (lds > 64 * 1024 && !nhwc) {
             hipError_t e = hipSuccess;
-            switch (f * 2 + cfg->out_dtype) {
-#define SETATTR(F, O) case F * 2 + O: e = hipFuncSetAttribute((const void*)evam_pp_kernel<F, O>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); break;
+            switch (f * 3 + out_kind(cfg->out_dtype)) {
+#define SETATTR(F, O) case F * 3 + O: e = hipFuncSetAttribute((const void*)evam_pp_kernel<F, O>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); break;
                 SETATTR(kNV12, 0) SETATTR(kNV12, 1) SETATTR(kI420, 0) SETATTR(kI420, 1)
                 SETATTR(kBGRX, 0) SETATTR(kBGRX, 1) SETATTR(kBGR, 0) SETATTR(kBGR, 1)
+                SETATTR(kNV12, 2) SETATTR(kI420, 2) SETATTR(kBGRX, 2) SETATTR(kBGR, 2)
 #undef SETATTR
             }
             if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));

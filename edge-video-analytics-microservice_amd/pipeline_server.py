@@ -218,7 +218,8 @@ class InferenceModel:
     ``fn(tensor) -> output``: for detection, an SSD ``DetectionOutput`` blob ``[N, K, 7]`` (boxes
     normalized to the input tensor). For classification, a dict ``{layer_name: [N, C]}`` or one
     ``[N, C]`` tensor. ``input_size`` is ``(W, H)``. Labels and pre-processing come from the
-    model-proc (``models_list/*.json``).
+    model-proc (``models_list/*.json``). ``out_dtype``: ``"f32"`` (default), ``"u8"``, or, for a model bound from
+    an ``FP16`` IR, ``"f16"`` / ``"bf16"``: the blob is then written in that type by the kernels (no cast pass).
     """
 
     fn: object
@@ -238,6 +239,8 @@ class InferenceModel:
                     entry = e
                     break
         info = PreProcInfo.from_model_proc(entry)
+        # the blob's type is this model's out_dtype, whatever precision the model-proc states
+        info.precision = {"f16": "FP16", "bf16": "BF16"}.get(self.out_dtype)
         for k, v in (overrides or {}).items():
             setattr(info, k, v)
         return info
@@ -848,7 +851,7 @@ class _InferenceStage:
         self.info = self.model.preproc_info()
 
     def out_dtype(self) -> int:
-        return N.DTYPE_F32 if self.model.out_dtype == "f32" else N.DTYPE_U8
+        return {"f32": N.DTYPE_F32, "f16": N.DTYPE_F16, "bf16": N.DTYPE_BF16}.get(self.model.out_dtype, N.DTYPE_U8)
 
     # A stage's work for one stream: prepare (gating / selection, on the caller's thread) -> run_batch over the
     # requests of every interchangeable stage (one launch) -> finish (per-stream bookkeeping).
@@ -893,7 +896,7 @@ class _InferenceStage:
         import torch
 
         W, H = self.model.input_size
-        dt = torch.float32 if self.model.out_dtype == "f32" else torch.uint8
+        dt = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}.get(self.model.out_dtype, torch.uint8)
         if self.model.layout not in ("nchw", "nhwc"):
             raise PreProcError(N.ERR_INVALID_ARG, f"model layout {self.model.layout!r} (nchw, nhwc)")
         fmt = torch.channels_last if self.model.layout == "nhwc" else torch.contiguous_format
@@ -1114,6 +1117,7 @@ class ActionRecognitionStage(_InferenceStage):
         self.dec_proc = json.load(open(mp)) if mp and os.path.exists(mp) else None
         if self.dec_proc:  # the decoder's model-proc carries the encoder's input_preproc too
             self.info = InferenceModel(None, self.model.input_size, self.dec_proc).preproc_info()
+        self.info.precision = None  # the clip ring stays fp32, whatever the encoder's out_dtype
 
     def _make_hub_key(self):
         return super()._make_hub_key() + ("clip", id(self.decoder) if self.decoder is not None else None)

@@ -163,6 +163,7 @@ class PreProcInfo:
     std: tuple | None = None            # per output channel
     placement: str = "top_left"         # letterbox placement: "top_left" | "center"
     fill: tuple = (0, 0, 0)             # u8 pad value per output channel
+    precision: str | None = None        # "FP16" | "BF16": a 16-bit output tensor (opt-in); anything else: as None
 
     @classmethod
     def from_model_proc(cls, entry: dict | None) -> "PreProcInfo":
@@ -183,6 +184,8 @@ class PreProcInfo:
             info.mean = tuple(float(v) for v in params["mean"])
         if "std" in params:
             info.std = tuple(float(v) for v in params["std"])
+        if "precision" in entry or "precision" in params:
+            info.precision = entry.get("precision", params.get("precision"))
         if "padding" in params:
             pad = params["padding"]
             if "fill_value" in pad:
@@ -274,6 +277,42 @@ class Transforms(_SequenceABC):
                          x.resized_w, x.resized_h)
 
 
+_PRECISION_DTYPE = {"FP16": N.DTYPE_F16, "BF16": N.DTYPE_BF16}
+_DTYPE_PRECISION = {v: k for k, v in _PRECISION_DTYPE.items()}
+
+
+def _pair_dtype(code: int, precision) -> int:
+    """The pairing rule of :func:`output_dtype` on a tensor's own dtype code."""
+    want = _PRECISION_DTYPE.get(precision) if isinstance(precision, str) else None
+    if code >= N.DTYPE_F16:
+        if want != code:
+            raise PreProcError(N.ERR_UNSUPPORTED,
+                               f"a 16-bit out tensor is lossy against the reference's fp32 input and is opt-in: state "
+                               f"PreProcInfo.precision={_DTYPE_PRECISION[code]!r} (got precision={precision!r})")
+    elif want is not None:
+        raise PreProcError(N.ERR_INVALID_ARG, f"precision={precision!r} needs a "
+                                              f"{'float16' if want == N.DTYPE_F16 else 'bfloat16'} out tensor")
+    return code
+
+
+def output_dtype(out, info: "PreProcInfo | None" = None) -> int:
+    """The ``evam_dtype`` code a call with output tensor ``out`` and ``info`` runs in.
+
+    uint8 and float32 tensors are ``DTYPE_U8`` / ``DTYPE_F32``. 16-bit output is opt-in, because it is one more
+    rounding than the fp32 tensor the reference hands its inference engine: a ``torch.float16`` / ``torch.bfloat16``
+    tensor needs ``info.precision`` ``"FP16"`` / ``"BF16"`` (else ``ERR_UNSUPPORTED``), and a stated ``"FP16"`` /
+    ``"BF16"`` with a tensor of any other dtype is ``ERR_INVALID_ARG``. Other ``precision`` values behave as ``None``.
+    Pure: reads only the tensor's dtype and ``info``."""
+    import torch
+
+    code = {torch.uint8: N.DTYPE_U8, torch.float32: N.DTYPE_F32, torch.float16: N.DTYPE_F16,
+            torch.bfloat16: N.DTYPE_BF16}.get(out.dtype)
+    if code is None:
+        raise PreProcError(N.ERR_UNSUPPORTED,
+                           f"out dtype {out.dtype} is not supported (uint8, float32; float16, bfloat16 with precision)")
+    return _pair_dtype(code, info.precision if info is not None else None)
+
+
 def tensor_layout(out) -> int:
     """``LAYOUT_NCHW`` or ``LAYOUT_NHWC`` of an ``[N,3,H,W]`` output tensor (``evam_tensor.layout``).
 
@@ -359,7 +398,7 @@ class HipPreProcessor:
                 self._stream_ptr = s
 
     def _tensor_desc(self, out, slot_offset: int, slot_stride: int):
-        """``byref`` of the validated evam_tensor for ``out``, and its dtype code. Cached per output tensor (a stage
+        """``byref`` of the validated evam_tensor for ``out``, and its own dtype's code. Cached per output tensor (a stage
         packs into the same inference blob every call; a runner or a bench cycles through a few): the same tensor
         object at the same version (``resize_`` / ``set_`` / ``as_strided_`` bump it) and storage has the shape,
         dtype, device and layout it was checked with, so they are not read again (~1 us per call)."""
@@ -371,6 +410,10 @@ class HipPreProcessor:
             t.slot_offset, t.slot_stride = int(slot_offset), int(slot_stride)
         return e[5], e[4]
 
+    def _check_device(self, out):
+        if out.device.type != "cuda" or (out.device.index or 0) != self.device:
+            raise PreProcError(N.ERR_INVALID_ARG, f"out must live on cuda:{self.device}, got {out.device}")
+
     def _tensor_entry(self, out):
         torch = self._torch
         layout = tensor_layout(out)
@@ -378,10 +421,14 @@ class HipPreProcessor:
             dt = N.DTYPE_U8
         elif out.dtype == torch.float32:
             dt = N.DTYPE_F32
+        elif out.dtype == torch.float16:  # the 16-bit types: convert() pairs them with info.precision
+            dt = N.DTYPE_F16
+        elif out.dtype == torch.bfloat16:
+            dt = N.DTYPE_BF16
         else:
-            raise PreProcError(N.ERR_UNSUPPORTED, f"out dtype {out.dtype} is not supported (uint8, float32)")
-        if out.device.type != "cuda" or (out.device.index or 0) != self.device:
-            raise PreProcError(N.ERR_INVALID_ARG, f"out must live on cuda:{self.device}, got {out.device}")
+            raise PreProcError(N.ERR_UNSUPPORTED,
+                               f"out dtype {out.dtype} is not supported (uint8, float32; float16, bfloat16 with precision)")
+        self._check_device(out)
         t = N.EvamTensor()
         t.data = out.data_ptr()
         t.n, t.c, t.h, t.w = (int(v) for v in out.shape)
@@ -395,7 +442,8 @@ class HipPreProcessor:
     # -- the hot path ------------------------------------------------------------------------------
     def convert(self, srcs, out, info: PreProcInfo | None = None, rois: Iterable | None = None,
                 slot_offset: int = 0, slot_stride: int = 1, want_transform: bool = False, slots=None):
-        """Pre-process ``srcs`` (or ``rois`` of them) into ``out`` ([N,3,H,W] uint8/float32, device).
+        """Pre-process ``srcs`` (or ``rois`` of them) into ``out`` ([N,3,H,W] uint8/float32, device; float16/bfloat16 with
+        ``info.precision`` ``"FP16"`` / ``"BF16"``, see :func:`output_dtype`).
 
         ``srcs``: an :class:`ImageBatch` (marshalled once) or a sequence of :class:`Image`.
         ``rois``: a :class:`RoiBatch`, an ``int32 [n, 5]`` array or a sequence of :class:`Roi`.
@@ -408,6 +456,8 @@ class HipPreProcessor:
         info = info or self._default_info
         batch = srcs if isinstance(srcs, ImageBatch) else ImageBatch(srcs)
         tref, dt = self._tensor_desc(out, slot_offset, slot_stride)
+        if dt >= N.DTYPE_F16 or info.precision is not None:
+            _pair_dtype(dt, info.precision)  # 16-bit output is opt-in (output_dtype); raises on a mismatch
         lc = self._last_cfg
         if lc is not None and lc[0] is info and lc[1] == dt and lc[2] == info.__dict__:
             cached = lc[3]  # the last call's info object, every field as it was (~1.3 us of key building saved)

@@ -9,6 +9,10 @@
  *     -> aspect-ratio letterbox / central crop (DL Streamer model-proc "resize"/"crop")
  *     -> optional BGR->RGB                    (model-proc "color_space")
  *     -> optional range + mean/std to fp32    (model-proc "range"/"mean"/"std")
+ *        or, opt-in, to fp16 / bf16: that fp32 value rounded once, to nearest even, for a model bound in FP16
+ *        (models_list/models.list.yml lists every model in FP16 and FP32). Planar 16-bit output runs on the same
+ *        kernel families as fp32; interleaved (NHWC) 16-bit output is served by the generic kernel only (three
+ *        element stores per pixel) — fast interleaved 16-bit variants are not built.
  *     -> planar NCHW write into batch slot n  (DL Streamer MatToMultiPlaneImage), or, with
  *        evam_tensor.layout = EVAM_LAYOUT_NHWC, the interleaved H x W x 3 image of that slot
  *        (Convert(..., make_planar = false): channels-last model input, published BGR frames)
@@ -93,7 +97,11 @@ enum evam_placement {
 };
 
 enum evam_color_order { EVAM_COLOR_BGR = 0, EVAM_COLOR_RGB = 1 };
-enum evam_dtype { EVAM_DTYPE_U8 = 0, EVAM_DTYPE_F32 = 1 };
+/* F16 / BF16: the fp32 value the F32 path stores, rounded once to the 16-bit type (round to nearest even; fp16 with
+ * subnormals and overflow to +-inf; NaN stays NaN, the sign of zero is kept). Everything that holds for F32 holds for
+ * them (norm_flags, range, mean, std, fill through the table, std[c] == 0 rejected); the element size is 2. A library
+ * built before they existed answers them with EVAM_PP_ERR_UNSUPPORTED (the ABI version is unchanged: no struct grew). */
+enum evam_dtype { EVAM_DTYPE_U8 = 0, EVAM_DTYPE_F32 = 1, EVAM_DTYPE_F16 = 2, EVAM_DTYPE_BF16 = 3 };
 
 #define EVAM_NORM_RANGE    1 /* f = (float)u8 * ((max-min)/255) + min      (OpenCV convertTo) */
 #define EVAM_NORM_MEAN_STD 2 /* f = (f - mean[c]) / std[c]                 (cv::subtract/divide) */
@@ -103,7 +111,7 @@ typedef struct evam_preproc {
     int32_t placement;     /* evam_placement (letterbox only)                                   */
     int32_t color_order;   /* evam_color_order of the output planes                             */
     int32_t out_dtype;     /* evam_dtype of the output tensor                                   */
-    int32_t norm_flags;    /* EVAM_NORM_* bits; ignored for U8 output                           */
+    int32_t norm_flags;    /* EVAM_NORM_* bits; ignored for U8 output (F32, F16 and BF16 apply them) */
     uint8_t fill[4];       /* u8 fill value of padded pixels, per OUTPUT channel, before normalisation */
     float range[2];        /* {min, max}                                                        */
     float mean[3];         /* per OUTPUT channel                                                */
@@ -192,6 +200,13 @@ int evam_pp_abi_version(void);
  * them on the device: ofs = clamped first tap (x axis) or raw floor (y axis), c0/c1 = 11-bit weights.
  * is_x != 0 applies OpenCV's x-axis border rule (fx = 0 at clamped taps). Host-only helper. */
 int evam_pp_linear_table(int src_size, int dst_size, int is_x, int32_t* ofs, int16_t* c0, int16_t* c1);
+
+/* The normalisation table the kernels map the resized u8 value through: 768 elements [c][u] (c = output channel,
+ * u = 0..255) in cfg->out_dtype, written to out: 4 bytes each for EVAM_DTYPE_F32, 2 for F16 / BF16 (the fp32 entry
+ * narrowed once, round to nearest even). evam_pp_run fills its device table from this same function. Only out_dtype,
+ * norm_flags, range, mean and std are read. EVAM_DTYPE_U8 (no table) and std[c] == 0 with EVAM_NORM_MEAN_STD are
+ * EVAM_PP_ERR_INVALID_ARG; an unknown dtype is EVAM_PP_ERR_UNSUPPORTED. Host-only helper. */
+int evam_pp_norm_table(const evam_preproc* cfg, void* out);
 
 #ifdef __cplusplus
 }
