@@ -9,12 +9,12 @@ After the first import the package is also reachable as ``evam_amd`` (``sys.modu
 
 Scope: decoded NV12/I420/BGRx/BGR frames -> colour conversion -> INTER_LINEAR /
 letterbox / central-crop resize -> ROI crop-resize -> normalisation -> NCHW (planar) or NHWC (interleaved:
-``torch.channels_last`` tensors, ``HipPreProcessor.export_bgr`` frames) batch packing, as hand-written HIP
-kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
+``torch.channels_last`` tensors, ``HipPreProcessor.export_bgr`` frames) batch packing, and baseline JPEG encoding of the published frame
+(``HipPreProcessor.encode_jpeg``), as hand-written HIP kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
 """
 import sys as _sys
 
-from ._native import PreProcError, load_library  # noqa: F401
+from ._native import PreProcError, jpeg_bound, jpeg_header, load_library  # noqa: F401
 from .preproc import (HipPreProcessor, Image, ImageBatch, PreProcInfo, Roi, RoiBatch, Transform,  # noqa: F401
                       create_preprocessor, output_dtype, plane_layout, tensor_layout)
 from . import _native as native  # noqa: F401

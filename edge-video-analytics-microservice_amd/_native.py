@@ -55,7 +55,10 @@ EXPORTED_SYMBOLS = (
     "evam_pp_create", "evam_pp_run", "evam_pp_run_slots", "evam_pp_sync", "evam_pp_set_stream", "evam_pp_set_option",
     "evam_pp_get_stats", "evam_pp_destroy", "evam_pp_last_error", "evam_pp_abi_version",
     "evam_pp_linear_table", "evam_pp_norm_table",
+    "evam_pp_jpeg_header", "evam_pp_encode_jpeg",
 )
+# ... and the one that returns size_t (tests/test_abi.py reads the header's int / void / const char* declarations)
+EXPORTED_SYMBOLS_SIZE_T = ("evam_pp_jpeg_bound",)
 
 c_i32 = ctypes.c_int32
 
@@ -94,6 +97,9 @@ class EvamStats(ctypes.Structure):
 # evam_pp_stats.kernels bits (include/evam_pp.h evam_kernel_family)
 KERNEL_GENERIC, KERNEL_ROWS, KERNEL_STAGED, KERNEL_WAVE = 1, 2, 4, 8
 KERNEL_STRIP, KERNEL_BAND, KERNEL_ROI = 16, 32, 64
+KERNEL_JPEG = 128
+
+JPEG_HEADER_LEN = 623  # SOI .. SOS of every file evam_pp_encode_jpeg writes
 
 
 STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32}
@@ -131,6 +137,13 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_linear_table.restype = ctypes.c_int
     lib.evam_pp_norm_table.argtypes = [P(EvamPreproc), vp]
     lib.evam_pp_norm_table.restype = ctypes.c_int
+    lib.evam_pp_jpeg_header.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t,
+                                        P(ctypes.c_size_t)]
+    lib.evam_pp_jpeg_header.restype = ctypes.c_int
+    lib.evam_pp_jpeg_bound.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.evam_pp_jpeg_bound.restype = ctypes.c_size_t
+    lib.evam_pp_encode_jpeg.argtypes = [vp, P(EvamImage), ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
+    lib.evam_pp_encode_jpeg.restype = ctypes.c_int
     return lib
 
 
@@ -162,6 +175,23 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     if path is None:
         _LIB = lib
     return lib
+
+
+def jpeg_header(width: int, height: int, quality: int) -> bytes:
+    """The 623 header bytes (SOI .. SOS) of a file ``evam_pp_encode_jpeg`` writes. Host-only."""
+    lib = load_library()
+    buf = (ctypes.c_uint8 * JPEG_HEADER_LEN)()
+    n = ctypes.c_size_t()
+    check(lib, lib.evam_pp_jpeg_header(int(width), int(height), int(quality), buf, JPEG_HEADER_LEN, ctypes.byref(n)))
+    return bytes(buf[:n.value])
+
+
+def jpeg_bound(width: int, height: int) -> int:
+    """Worst-case bytes of one encoded ``width`` x ``height`` frame, header and EOI included. Host-only."""
+    n = int(load_library().evam_pp_jpeg_bound(int(width), int(height)))
+    if n == 0:
+        raise PreProcError(ERR_INVALID_ARG, f"jpeg_bound: bad frame size {width}x{height}")
+    return n
 
 
 class PreProcError(RuntimeError):

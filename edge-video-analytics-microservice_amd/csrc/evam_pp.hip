@@ -4081,6 +4081,8 @@ struct HipRings {
 using DescRing = DescRingT<HipRings>;
 using PinRing = PinRingT<HipRings>;
 
+#include "evam_jpeg_kernels.h"
+
 }  // namespace
 
 #ifdef EVAM_PP_HOST_PROF
@@ -4131,6 +4133,7 @@ struct evam_pp {
     std::vector<YTab> sc_yt;
     int nhwc_key[4][16] = {};      // per format: what the last interleaved uniform group's choice depended on
     int nhwc_ok[4] = {-1, -1, -1, -1};  // ... and the choice: 1 strip / wave kernel, 0 generic kernel (-1: none yet)
+    JpegScratch jpeg;              // evam_pp_encode_jpeg: device scratch and the tables' key
 };
 
 namespace {
@@ -4224,6 +4227,8 @@ void evam_pp_destroy(evam_pp* h) {
     HipRings b;
     h->ring.release(b);
     h->pin.release(b);
+    for (void* p : h->jpeg.buf)
+        if (p) (void)hipFree(p);  // waits for kernels that still use it
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -5164,3 +5169,5 @@ int evam_pp_run_slots(evam_pp* h, const evam_image* srcs, int n_srcs, const evam
 }
 
 }  // extern "C"
+
+#include "evam_jpeg_api.h"

@@ -1249,6 +1249,31 @@ class PipelineDefinition:
                    d.get("description", ""), d.get("parameters", {}))
 
 
+
+def publisher_encoding(destination):
+    """``None``, or ``("jpeg", level)`` of a destination whose ``"encoding": {"type": "jpeg", "level": N}`` asks for
+    encoded published frames (the reference publisher's ``encoding`` config, ``evas/publisher.py:105-151``). The
+    reference logs a bad config and then fails on the first frame; here it is refused when the pipeline starts:
+    ``"png"`` (not built) or an unknown type is ``ERR_UNSUPPORTED``; a missing / non-integer level, one outside
+    0..100, or ``"encoding"`` on a destination that is not in ``"publisher"`` mode is ``ERR_INVALID_ARG``."""
+    from . import _native as N
+
+    dst = (destination or {}).get("metadata", destination or {})
+    enc = dst.get("encoding")
+    if enc is None:
+        return None
+    if dst.get("mode") != "publisher":
+        raise N.PreProcError(N.ERR_INVALID_ARG, f"destination \"encoding\" needs mode \"publisher\", got {dst.get('mode')!r}")
+    if not isinstance(enc, dict) or "type" not in enc or "level" not in enc:
+        raise N.PreProcError(N.ERR_INVALID_ARG, f"destination \"encoding\" must be {{\"type\", \"level\"}}, got {enc!r}")
+    kind, level = enc["type"], enc["level"]
+    if kind != "jpeg":
+        raise N.PreProcError(N.ERR_UNSUPPORTED, f"encoding type {kind!r} is not supported (\"jpeg\" only; PNG is not built)")
+    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level <= 100:
+        raise N.PreProcError(N.ERR_INVALID_ARG, f"jpeg encoding level must be an integer in 0..100, got {level!r}")
+    return kind, level
+
+
 class Pipeline:
     """One pipeline instance (``PipelineServer.pipeline(name, version)``)."""
 
@@ -1281,6 +1306,7 @@ class Pipeline:
         self._out_backlog = collections.deque()  # runner mode: results a full destination queue could not take
         self._out_limit = 1  # held-back results at which the runner stops ingesting / running this stream
         self._export_pp = None    # destination mode "publisher": this pipeline's handle for export_bgr
+        self._encoding = None     # ... and its ("jpeg", level) when the destination asks for encoded frames
         self._export_host = None  # ... and its pinned host buffer for a tick's packed BGR frames
         # logical device: pipeline k of the server runs on devices[(k - 1) mod G] (streams partitioned over GPUs)
         self.slot = server.slot_for(instance_id)
@@ -1312,6 +1338,7 @@ class Pipeline:
     # -- execution ---------------------------------------------------------------------------
     def start(self, source=None, destination=None, parameters=None):
         """Build the element graph, instantiate the HIP stages, and run the frame loop in a thread."""
+        self._encoding = publisher_encoding(destination)  # refused here, before anything runs
         self.build(source, parameters)
         self.stages = [STAGES[e.factory](e, self.server, self.device, self.slot)
                        for e in self.elements if e.factory in STAGES]
@@ -1410,7 +1437,8 @@ class Pipeline:
 
     def _export_frames(self, items):
         """Destination mode ``"publisher"``: the packed H*W*3 BGR image (bytes) of every frame of ``items``, in
-        order. One ``export_bgr`` launch per run of equal-sized frames (a stream's frames share a size: one launch
+        order; with ``"encoding": {"type": "jpeg", "level": N}`` its JFIF file instead (``encode_jpeg``, encoded on
+        the device: only the file crosses PCIe). One ``export_bgr`` launch per run of equal-sized frames (a stream's frames share a size: one launch
         per tick), one copy into this pipeline's pinned host buffer and one stream synchronisation per launch —
         a synchronous copy per tick, accepted for this opt-in mode."""
         import torch
@@ -1427,6 +1455,10 @@ class Pipeline:
             e = k + 1
             while e < len(items) and items[e][1].width == w and items[e][1].height == h:
                 e += 1
+            if self._encoding is not None:
+                out.extend(self._export_pp.encode_jpeg([it[1] for it in items[k:e]], self._encoding[1]))
+                k = e
+                continue
             dev = self._export_pp.export_bgr([it[1] for it in items[k:e]])
             total, each = dev.numel(), h * w * 3
             if self._export_host is None or self._export_host.numel() < total:
@@ -1516,7 +1548,7 @@ class Pipeline:
         if mode == "frames":
             item = (img, fr)
         elif mode == "publisher":
-            item = P.publisher_message(fr, frame)
+            item = P.publisher_message(fr, frame, encoding=self._encoding)
         else:
             item = P.gvametaconvert_json(fr)
         if self._runner:

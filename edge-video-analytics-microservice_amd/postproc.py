@@ -207,8 +207,9 @@ def gvametaconvert_json(fr: FrameResult) -> str:
     return json.dumps(gvametaconvert(fr), sort_keys=True, separators=(",", ":"))
 
 
-def publisher_meta(fr: FrameResult, caps: str = "", img_handle: str = "") -> dict:
-    """The EVAM publisher's per-frame metadata dict (``evas/publisher.py:183-230``)."""
+def publisher_meta(fr: FrameResult, caps: str = "", img_handle: str = "", encoding=None) -> dict:
+    """The EVAM publisher's per-frame metadata dict (``evas/publisher.py:183-230``). ``encoding``: ``None``, or the
+    ``(type, level)`` the frame was encoded with, added as ``encoding_type`` / ``encoding_level`` (``:235-236``)."""
     meta = {"height": fr.height, "width": fr.width, "channels": 3, "caps": caps, "img_handle": img_handle}
     for m in fr.messages:
         meta.update(json.loads(m) if isinstance(m, str) else m)
@@ -222,6 +223,8 @@ def publisher_meta(fr: FrameResult, caps: str = "", img_handle: str = "") -> dic
             tens.append(tm)
         gva.append({"x": r.x, "y": r.y, "height": r.h, "width": r.w, "object_id": r.object_id, "tensor": tens})
     meta["gva_meta"] = gva
+    if encoding is not None:
+        meta["encoding_type"], meta["encoding_level"] = encoding
     return meta
 
 
@@ -239,13 +242,15 @@ def image_handle(n: int = 10) -> str:
     return "".join(random.choices(_HANDLE_ALPHABET, k=n))
 
 
-def publisher_message(fr: FrameResult, frame, caps: str | None = None, img_handle: str | None = None) -> tuple:
+def publisher_message(fr: FrameResult, frame, caps: str | None = None, img_handle: str | None = None,
+                      encoding=None) -> tuple:
     """The ``(meta, frame)`` tuple the EVAM publisher sends with ``publish_frame`` set (``evas/publisher.py:
     142-143,246-250``): ``publisher_meta`` plus the packed ``H*W*3`` BGR image of the frame (bytes, or any buffer;
     ``HipPreProcessor.export_bgr`` produces it on the device). ``caps`` defaults to the BGR caps of the frame's
-    size, ``img_handle`` to a fresh 10-character handle."""
+    size, ``img_handle`` to a fresh 10-character handle. With ``encoding`` = ``(type, level)``, ``frame`` is the
+    encoded file (``HipPreProcessor.encode_jpeg``) and the meta says so."""
     if caps is None:
         caps = publisher_caps(fr.width, fr.height)
     if img_handle is None:
         img_handle = image_handle(10)
-    return publisher_meta(fr, caps, img_handle), frame
+    return publisher_meta(fr, caps, img_handle, encoding), frame

@@ -355,6 +355,10 @@ class HipPreProcessor:
         self._tdesc: dict = {}  # id(output tensor) -> (weakref, version, data_ptr, evam_tensor, dtype code, byref)
         self._default_info = PreProcInfo()
         self._export_info: dict = {}  # color_space -> the PreProcInfo of export_bgr (identity resize, u8)
+        self._jpeg_dev = None   # encode_jpeg: (uint8 [n, stride] slots, uint32 [n] sizes) on the device
+        self._jpeg_host = None  # ... and their pinned host mirrors
+        self._jpeg_need = {}    # (width, height) -> slot bytes, once files of that size outgrew the default slot
+        self._jpeg_guess = 0    # bytes of every slot the next encode_jpeg copies to the host first
         self._run = self._lib.evam_pp_run
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
         self._raw_stream = raw if raw is not None else (
@@ -527,6 +531,111 @@ class HipPreProcessor:
             info = self._export_info[color_space] = PreProcInfo(resize="no-aspect-ratio", color_space=color_space)
         self.convert(batch, out.permute(0, 3, 1, 2), info)
         return out
+
+
+    # -- JPEG encoding of the published frame ------------------------------------------------------------
+    @staticmethod
+    def _jpeg_args(srcs, quality):
+        """(ImageBatch, width, height) of an encode call; every refusal that needs no device happens here."""
+        batch = srcs if isinstance(srcs, ImageBatch) else ImageBatch(srcs)
+        if len(batch) == 0:
+            raise PreProcError(N.ERR_INVALID_ARG, "encode_jpeg: no frames")
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
+            raise PreProcError(N.ERR_INVALID_ARG, f"encode_jpeg: quality must be an integer in 0..100, got {quality!r}")
+        w, h = batch.images[0].width, batch.images[0].height
+        for im in batch.images:
+            if im.width != w or im.height != h:
+                raise PreProcError(N.ERR_INVALID_ARG, f"encode_jpeg: frames of one call must share a size, got "
+                                                      f"{w}x{h} and {im.width}x{im.height}")
+        return batch, w, h
+
+    def encode_jpeg_into(self, srcs, out, sizes, quality: int = 95):
+        """Encode every frame of ``srcs`` as a baseline JFIF file (what the reference's publisher gets from
+        ``cv2.imencode('.jpg', frame, [IMWRITE_JPEG_QUALITY, quality])``) into row i of ``out`` (uint8 ``[n, stride]``,
+        device, contiguous); ``sizes`` (int32 / uint32-as-int32 ``[n]``, device) receives every file's full length, also
+        when it exceeds ``stride`` (that row is then incomplete: encode again with ``N.jpeg_bound``). Asynchronous, as
+        :meth:`convert`."""
+        batch, _, _ = self._jpeg_args(srcs, quality)  # refusals first: they need no device
+        torch = self._torch
+        n = len(batch)
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] < n or not out.is_contiguous():
+            raise PreProcError(N.ERR_INVALID_ARG, f"encode_jpeg_into: out must be a contiguous uint8 [>= {n}, stride] "
+                                                  f"tensor, got {out.dtype} {tuple(out.shape)}")
+        if sizes.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or sizes.dim() != 1 \
+                or sizes.shape[0] < n or not sizes.is_contiguous():
+            raise PreProcError(N.ERR_INVALID_ARG, f"encode_jpeg_into: sizes must be a contiguous 32-bit integer [>= {n}] "
+                                                  f"tensor, got {sizes.dtype} {tuple(sizes.shape)}")
+        self._check_device(out)
+        self._check_device(sizes)
+        self._bind_stream()
+        rc = self._lib.evam_pp_encode_jpeg(self._h, batch.c_array, n, int(quality), ctypes.c_void_p(out.data_ptr()),
+                                           int(out.shape[1]), ctypes.c_void_p(sizes.data_ptr()))
+        if rc:
+            N.check(self._lib, rc)
+
+    def _jpeg_buffers(self, n: int, stride: int):
+        torch = self._torch
+        d = self._jpeg_dev
+        if d is None or d[0].shape[0] < n or d[0].shape[1] < stride:
+            n_cap = max(n, d[0].shape[0] if d is not None else 0)
+            s_cap = max(stride, d[0].shape[1] if d is not None else 0)
+            dev = f"cuda:{self.device}"
+            self._jpeg_dev = (torch.empty((n_cap, s_cap), dtype=torch.uint8, device=dev),
+                              torch.empty((n_cap,), dtype=torch.int32, device=dev))
+            self._jpeg_host = (torch.empty((n_cap, s_cap), dtype=torch.uint8, pin_memory=True),
+                               torch.empty((n_cap,), dtype=torch.int32, pin_memory=True))
+        return self._jpeg_dev, self._jpeg_host
+
+    def encode_jpeg(self, srcs, quality: int = 95) -> list:
+        """The JFIF file of every frame of ``srcs`` as ``bytes``: one launch sequence, one stream synchronisation (a
+        second only when the files outgrow what the last call's sizes predicted), device slots and pinned host staging
+        owned by this object. A slot holds ``1024 + W16 * H16`` bytes (one per
+        pixel of the frame padded to whole MCUs); frames that need more (noise at high quality) are encoded again with
+        the worst-case bound, so the result is always complete; later calls at that size then start with slots a
+        quarter larger than the largest such file."""
+        import numpy as np
+
+        batch, w, h = self._jpeg_args(srcs, quality)  # refusals first: they need no device
+        torch = self._torch
+        n = len(batch)
+        stride = max(1024 + (-(-w // 16) * 16) * (-(-h // 16) * 16), self._jpeg_need.get((w, h), 0))
+        (d_out, d_sizes), (h_out, h_sizes) = self._jpeg_buffers(n, stride)
+        d_rows = d_out.view(-1)[:n * stride].view(n, stride)
+        self.encode_jpeg_into(batch, d_rows, d_sizes, quality)
+        # Only the head of every slot crosses PCIe: as many bytes as the largest file of the last call plus a quarter
+        # (the whole slot the first time). A call whose files outgrow that fetches the rest in a second copy.
+        g = min(stride, self._jpeg_guess or stride)
+        head = d_rows if g == stride else d_rows[:, :g].contiguous()
+        h_rows = h_out.view(-1)[:n * g].view(n, g)
+        if not self._follow_torch_stream:  # a stream given at construction: the copies below run on torch's
+            self.sync()
+        h_sizes[:n].copy_(d_sizes[:n], non_blocking=True)
+        h_rows.copy_(head, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        lens = h_sizes[:n].numpy().astype(np.int64) & 0xFFFFFFFF
+        rows = h_rows.numpy()
+        need = int(min(stride, lens.max()))
+        if need > g:
+            rows = np.concatenate([rows, d_rows[:, g:need].cpu().numpy()], axis=1)
+        self._jpeg_guess = min(stride, -(-(need + need // 4) // 4096) * 4096)
+        files = [rows[i, :lens[i]].tobytes() if lens[i] <= stride else None for i in range(n)]
+        over = [i for i, f in enumerate(files) if f is None]
+        if over:
+            big = N.jpeg_bound(w, h)
+            d_rows = torch.empty((len(over), big), dtype=torch.uint8, device=d_out.device)
+            self.encode_jpeg_into([batch.images[i] for i in over], d_rows, d_sizes, quality)
+            if not self._follow_torch_stream:
+                self.sync()
+            lens2 = d_sizes[:len(over)].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+            got = d_rows[:, :int(lens2.max())].cpu().numpy()
+            for k, i in enumerate(over):
+                files[i] = got[k, :lens2[k]].tobytes()
+            # frames of this size outgrew the default slot: the next calls start with room for them
+            if len(self._jpeg_need) >= 16:
+                self._jpeg_need.clear()
+            top = int(lens2.max())
+            self._jpeg_need[(w, h)] = min(big, -(-(top + top // 4) // 4096) * 4096)
+        return files
 
 
 # Backend registry keyed by the DL Streamer element property value `pre-process-backend`.

@@ -160,7 +160,8 @@ typedef struct evam_pp_stats {
 /* evam_pp_stats.kernels bits (diagnostics: which kernel family served a call). */
 enum evam_kernel_family {
     EVAM_KERNEL_GENERIC = 1, EVAM_KERNEL_ROWS = 2, EVAM_KERNEL_STAGED = 4, EVAM_KERNEL_WAVE = 8,
-    EVAM_KERNEL_STRIP = 16, EVAM_KERNEL_BAND = 32, EVAM_KERNEL_ROI = 64
+    EVAM_KERNEL_STRIP = 16, EVAM_KERNEL_BAND = 32, EVAM_KERNEL_ROI = 64,
+    EVAM_KERNEL_JPEG = 128 /* evam_pp_encode_jpeg: set beside the bits of the export that staged the BGR frame */
 };
 
 enum evam_pp_option {
@@ -207,6 +208,35 @@ int evam_pp_linear_table(int src_size, int dst_size, int is_x, int32_t* ofs, int
  * norm_flags, range, mean and std are read. EVAM_DTYPE_U8 (no table) and std[c] == 0 with EVAM_NORM_MEAN_STD are
  * EVAM_PP_ERR_INVALID_ARG; an unknown dtype is EVAM_PP_ERR_UNSUPPORTED. Host-only helper. */
 int evam_pp_norm_table(const evam_preproc* cfg, void* out);
+
+/* ---- JPEG encoding of the published frame (the reference's publisher: cv2.imencode('.jpg', frame,
+ * [IMWRITE_JPEG_QUALITY, level]), evas/publisher.py:127-151). Added without a struct change, so the ABI version
+ * stays 3; a library built before them lacks the symbols.
+ *
+ * The file is what libjpeg writes with its defaults: baseline JFIF 1.01, 4:2:0, JDCT_ISLOW, the Annex K Huffman
+ * tables, no restart interval, quantisation tables of jpeg_set_quality(quality, TRUE) (a quality <= 0 counts as 1).
+ * The pixels are the frame evam_pp_run publishes as an identity BGR u8 export, converted by libjpeg's integer
+ * RGB -> YCbCr. tests/jpeg_ref.py restates the arithmetic and is pinned byte for byte to libjpeg-turbo files. */
+
+/* The 623 bytes every file of (width, height, quality) starts with: SOI, APP0, two DQT, SOF0, four DHT, SOS.
+ * *len is set to 623 whenever len is given; out must hold that many (cap). Host-only helper. */
+int evam_pp_jpeg_header(int width, int height, int quality, uint8_t* out, size_t cap, size_t* len);
+
+/* Worst-case bytes of one encoded frame, header and EOI included: a block codes to at most 1,660 bits (DC 11 + 11,
+ * AC 63 x (16 + 10)), doubled for byte stuffing, six blocks per 16x16 MCU. 0 for a size evam_pp_run refuses.
+ * Host-only helper. */
+size_t evam_pp_jpeg_bound(int width, int height);
+
+/* Encode every frame of srcs (one size per call; any fourcc evam_pp_run accepts, full frame, source size) as one
+ * JFIF file each. Frame i's file starts at dst + i*dst_stride (device memory). sizes[i] (device, uint32) is its full
+ * length in bytes, also when that exceeds dst_stride: then nothing is written outside the slot, the slot's contents
+ * are unspecified, and the caller retries with a larger stride (evam_pp_jpeg_bound always suffices).
+ * quality: 0..100. EVAM_PP_ERR_INVALID_ARG: another quality, frames of different sizes, n_srcs outside 1..65535, a
+ * null pointer, dst_stride smaller than the header plus 2, a frame of more than 2^32 / 1660 blocks. Sources are
+ * validated as evam_pp_run validates them, with its status codes. Scratch belongs to the handle, grows on demand and
+ * is reused (EVAM_PP_ERR_OOM when it cannot). Asynchronous on the handle's stream. */
+int evam_pp_encode_jpeg(evam_pp* h, const evam_image* srcs, int n_srcs, int quality,
+                        void* dst, size_t dst_stride, uint32_t* sizes);
 
 #ifdef __cplusplus
 }
