@@ -128,9 +128,9 @@ struct alignas(16) ColEntry {  // 16 B
 // Per output row of a tile: byte offsets of the two vertical taps' rows inside the planes.
 struct alignas(16) RowEntry {  // 32 B
     int32_t y0, y1;   // row offsets in the luma / packed plane (always valid addresses)
-    int32_t c0, c1;   // row offsets in the chroma plane(s) (I420: same offset for U and V)
+    int32_t c0, c1;   // row offsets in the chroma plane (NV12: UV; I420: U)
     int32_t b0, b1;   // 11-bit vertical weights << 8 (see vresize); both 0: the row shows padding
-    int32_t pad0, pad1;
+    int32_t v0, v1;   // I420: row offsets in the V plane, which has its own pitch; else 0
 };
 
 // Per-item arguments of the uniform-geometry kernels (staged / wave / rows), carried in the launch's
@@ -251,14 +251,15 @@ struct FmtTraits {
 // Plane bases are wave-uniform (SGPR) and offsets 32-bit, so each load is one saddr-form instruction.
 template <int FMT>
 __device__ __forceinline__ void load_tap(const uint8_t* __restrict__ p0, const uint8_t* __restrict__ p1,
-                                         const uint8_t* __restrict__ p2, uint32_t oy, uint32_t oc, uint32_t (&v)[3]) {
+                                         const uint8_t* __restrict__ p2, uint32_t oy, uint32_t oc, uint32_t ov,
+                                         uint32_t (&v)[3]) {
     if constexpr (FMT == kNV12) {
         v[0] = p0[oy];
         v[1] = *reinterpret_cast<const uint16_t*>(p1 + oc);
     } else if constexpr (FMT == kI420) {
         v[0] = p0[oy];
         v[1] = p1[oc];
-        v[2] = p2[oc];
+        v[2] = p2[ov];
     } else if constexpr (FMT == kBGRX) {
         v[0] = *reinterpret_cast<const uint32_t*>(p0 + oy);
     } else {
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
     const uint8_t* __restrict__ p0 = it->plane[0];
     const uint8_t* __restrict__ p1 = it->plane[1];
     const uint8_t* __restrict__ p2 = it->plane[2];
-    const int pitch0 = it->pitch[0], pitch1 = it->pitch[1];
+    const int pitch0 = it->pitch[0], pitch1 = it->pitch[1], pitch2 = it->pitch[2];
     const int x0 = it->x0, y0 = it->y0, cw = it->cw, ch = it->ch;
     const int rw = it->rw, rh = it->rh, ox = it->ox, oy = it->oy;
     const double scx = it->scale_x, scy = it->scale_y;
@@ -395,12 +396,13 @@ __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
             e.y1 = yb * pitch0;
             e.c0 = (ya >> 1) * pitch1;
             e.c1 = (yb >> 1) * pitch1;
+            e.v0 = FMT == kI420 ? (ya >> 1) * pitch2 : 0;
+            e.v1 = FMT == kI420 ? (yb >> 1) * pitch2 : 0;
             e.b0 = b0 << 8;
             e.b1 = b1 << 8;
         } else {
-            e.y0 = 0; e.y1 = 0; e.c0 = 0; e.c1 = 0; e.b0 = 0; e.b1 = 0;
+            e.y0 = 0; e.y1 = 0; e.c0 = 0; e.c1 = 0; e.b0 = 0; e.b1 = 0; e.v0 = 0; e.v1 = 0;
         }
-        e.pad0 = 0; e.pad1 = 0;
         rowtab[ly] = e;
     }
     __syncthreads();
@@ -440,10 +442,12 @@ __global__ __launch_bounds__(kThreads) void evam_pp_kernel(const KParams P) {
         }
         // Table offsets are valid addresses even for padding / out-of-tile lanes: no selects here.
         const uint32_t oc1 = FMT == kNV12 ? ((uint32_t)ce.oY1 & ~1u) : ((uint32_t)ce.oY1 >> 1);  // tap-1 chroma
-        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y0 + ce.oY0), (uint32_t)(re.c0 + ce.oC0), x.raw[0]);
-        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y0 + ce.oY1), (uint32_t)re.c0 + oc1, x.raw[1]);
-        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y1 + ce.oY0), (uint32_t)(re.c1 + ce.oC0), x.raw[2]);
-        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y1 + ce.oY1), (uint32_t)re.c1 + oc1, x.raw[3]);
+        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y0 + ce.oY0), (uint32_t)(re.c0 + ce.oC0), (uint32_t)(re.v0 + ce.oC0),
+                      x.raw[0]);
+        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y0 + ce.oY1), (uint32_t)re.c0 + oc1, (uint32_t)re.v0 + oc1, x.raw[1]);
+        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y1 + ce.oY0), (uint32_t)(re.c1 + ce.oC0), (uint32_t)(re.v1 + ce.oC0),
+                      x.raw[2]);
+        load_tap<FMT>(p0, p1, p2, (uint32_t)(re.y1 + ce.oY1), (uint32_t)re.c1 + oc1, (uint32_t)re.v1 + oc1, x.raw[3]);
     };
     auto finish = [&](const Px& x) {
         if (x.mode == 0) return;

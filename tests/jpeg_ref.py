@@ -203,13 +203,15 @@ def _category(v: int) -> int:
 
 def encode(bgr_u8: np.ndarray, quality: int):
     """(JFIF bytes, stats) of an [H, W, 3] uint8 BGR image. stats: zrl, stuffed, max_category, dummy_blocks,
-    min_block_bits."""
+    min_block_bits, max_dc_category (the largest DC-difference category), max_zrl_run (the most ZRL codes in front of
+    one AC coefficient), no_eob_blocks (blocks whose coefficient 63 is non-zero: they end without an EOB)."""
     bgr = np.ascontiguousarray(bgr_u8)
     assert bgr.dtype == np.uint8 and bgr.ndim == 3 and bgr.shape[2] == 3
     h, w = bgr.shape[:2]
     coef, dummies = coefficients(bgr, quality)
     codes, lens = [], []
-    stats = {"zrl": 0, "stuffed": 0, "max_category": 0, "dummy_blocks": dummies, "min_block_bits": 1 << 30}
+    stats = {"zrl": 0, "stuffed": 0, "max_category": 0, "dummy_blocks": dummies, "min_block_bits": 1 << 30,
+             "max_dc_category": 0, "max_zrl_run": 0, "no_eob_blocks": 0}
     pred = [0, 0, 0]
     flat = coef.reshape(-1, 64).tolist()
     for bi, blk in enumerate(flat):
@@ -221,6 +223,7 @@ def encode(bgr_u8: np.ndarray, quality: int):
         pred[comp] = blk[0]
         s = _category(v)
         stats["max_category"] = max(stats["max_category"], s)
+        stats["max_dc_category"] = max(stats["max_dc_category"], s)
         c, ln = dc[s]
         codes.append(c)
         lens.append(ln)
@@ -233,6 +236,7 @@ def encode(bgr_u8: np.ndarray, quality: int):
             if v == 0:
                 run += 1
                 continue
+            stats["max_zrl_run"] = max(stats["max_zrl_run"], run >> 4)
             while run > 15:
                 c, ln = ac[0xF0]
                 codes.append(c)
@@ -251,6 +255,8 @@ def encode(bgr_u8: np.ndarray, quality: int):
             c, ln = ac[0x00]
             codes.append(c)
             lens.append(ln)
+        else:
+            stats["no_eob_blocks"] += 1
         stats["min_block_bits"] = min(stats["min_block_bits"], sum(lens[n0:]))
     codes = np.asarray(codes, np.int64)
     lens = np.asarray(lens, np.int64)

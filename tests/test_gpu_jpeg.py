@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import jpeg_ref
+from jpeg_content import content
 from test_gpu_parity import fc, upload
 from test_pipeline_server import PIPES, make_model_tree
 
@@ -40,20 +41,6 @@ def bgr_frame(O, img, fmt="BGR", seed=0):
 
 def expected(O, frame, quality):
     return jpeg_ref.encode(O.np_to_bgr(frame, 0, 0, frame.width, frame.height), quality)
-
-
-def content(kind, w, h, seed=0):
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:h, 0:w]
-    if kind == "noise":
-        return rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-    if kind == "sat":
-        return (rng.integers(0, 2, (h, w, 3), dtype=np.uint8) * 255).astype(np.uint8)
-    if kind == "checker":
-        return np.repeat((((x + y) & 1) * 255).astype(np.uint8)[..., None], 3, -1)
-    if kind == "const":
-        return np.broadcast_to(np.array([37, 150, 201], np.uint8), (h, w, 3)).copy()
-    return np.stack([(x * 255) // max(w - 1, 1), (y * 255) // max(h - 1, 1), ((x + y) * 3) % 256], -1).astype(np.uint8)
 
 
 def check(evam, O, gpu, pp, frames, quality, what):

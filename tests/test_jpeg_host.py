@@ -1,7 +1,7 @@
 """JPEG encoding, host side: the numpy restatement of libjpeg (tests/jpeg_ref.py) pinned byte for byte to the files
 libjpeg-turbo wrote (tests/golden/jpeg, through Pillow; tests/golden/jpeg/generate.py), the library's host helpers
 against the same files, the refusals that need no device, and the pipeline server's "encoding" option with a stand-in
-pre-processor. The kernels are covered by tests/test_gpu_jpeg.py."""
+pre-processor. The kernels are covered by tests/test_gpu_jpeg.py and tests/test_gpu_jpeg_sweep.py."""
 import glob
 import io
 import os
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import jpeg_ref
+from jpeg_content import CUT_FRAMES, content, cut_strides
 from test_pipeline_runner import StubPP, register, stubbed  # noqa: F401  (stubbed: fixture)
 from test_pipeline_server import PIPES
 
@@ -44,7 +45,8 @@ def test_golden_set_is_complete():
 def test_ref_equals_golden(name, img, q, ref):
     got, stats = jpeg_ref.encode(img, q)
     assert got == ref
-    assert set(stats) == {"zrl", "stuffed", "max_category", "dummy_blocks", "min_block_bits"}
+    assert set(stats) == {"zrl", "stuffed", "max_category", "dummy_blocks", "min_block_bits", "max_dc_category",
+                          "max_zrl_run", "no_eob_blocks"}
 
 
 def test_ref_stats_see_the_hard_parts():
@@ -54,6 +56,36 @@ def test_ref_stats_see_the_hard_parts():
     assert by["checker_48x32_q10"]["zrl"] > 0
     assert by["sat_50x34_q100"]["max_category"] >= 10 and by["sat_50x34_q100"]["stuffed"] > 0
     assert by["noise_18x18_q10"]["dummy_blocks"] == 7 and by["grad_16x16_q95"]["dummy_blocks"] == 0
+
+
+def test_ref_stats_of_the_sweep_contents():
+    """What tests/test_gpu_jpeg_sweep.py asserts before it trusts a case, on the reference alone: DC category 11,
+    three ZRL codes in front of one coefficient, blocks that end without an EOB, quality 0 as quality 1, the file
+    that outgrows encode_jpeg's default slot, and cuts that fall behind a stuffed 0xFF. The counts are additions to
+    ``encode``'s stats, so the golden files must still reproduce."""
+    for name, img, q, ref in CASES:
+        assert jpeg_ref.encode(img, q)[0] == ref, name
+    _, st = jpeg_ref.encode(content("blocks", 48, 32), 100)
+    assert st["max_dc_category"] == 11 == st["max_category"]
+    _, st = jpeg_ref.encode(content("lowchecker", 48, 32), 10)
+    # coefficient 63 is the only AC coefficient of those 24 blocks: 62 zeros = 3 ZRL + a run of 14, and no EOB
+    assert st["max_zrl_run"] == 3 and st["no_eob_blocks"] == 24 and st["zrl"] == 72 and st["max_category"] == 1
+    f1, st = jpeg_ref.encode(content("checker", 48, 32), 1)
+    assert st["max_zrl_run"] == 2
+    assert jpeg_ref.encode(content("checker", 48, 32), 0)[0] == f1
+    f, st = jpeg_ref.encode(content("sat", 50, 34, 3), 100)
+    assert st["no_eob_blocks"] == 51 and st["dummy_blocks"] == 13 and st["max_dc_category"] == 10
+    assert len(f) == 5573 > 1024 + 64 * 48
+    assert len(jpeg_ref.encode(content("const", 50, 34), 100)[0]) <= 1024 + 64 * 48
+    # a plain scan: no ZRL, every block ends with an EOB
+    _, st = jpeg_ref.encode(content("const", 48, 32), 95)
+    assert (st["max_zrl_run"], st["no_eob_blocks"], st["zrl"]) == (0, 0, 0)
+    stuffed_cuts = 0
+    for kind, w, h, seed, q in CUT_FRAMES:
+        f, _ = jpeg_ref.encode(content(kind, w, h, seed), q)
+        assert f[-2:] == b"\xFF\xD9" and len(f) > 625 + 3
+        stuffed_cuts += sum(f[s - 1] == 0xFF and f[s] == 0x00 for s in cut_strides(len(f)) if s < len(f) - 1)
+    assert stuffed_cuts >= 2
 
 
 def test_ref_equals_fresh_pillow():
