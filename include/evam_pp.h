@@ -68,7 +68,15 @@ enum evam_pp_status {
 /* A decoded frame. Planes are DEVICE pointers; plane i has pitch[i] bytes per row.
  * NV12: planes[0]=Y, planes[1]=UV.  I420: Y, U, V.  BGRx/BGRA/BGR: planes[0] only.
  * YUV 4:2:0 frames must have even width and height (as OpenCV's YUV420 conversions require).
- * Every used plane pointer and pitch must be a multiple of 16 bytes. */
+ * Every used plane pointer and pitch must be a multiple of 16 bytes; nothing more is assumed about them. Every plane
+ * has its own pitch, at least its row bytes (NV12's UV pitch need not equal its Y pitch, I420's U and V pitches need
+ * not be equal nor half the Y pitch), and the frames of one call need not share pitches. The planes of a frame may lie
+ * in any order and at any distance in memory (chroma below luma, V below U, separate allocations), and a frame may be
+ * a window of a larger surface: plane pointers into its interior, the surface's pitch as the pitch. The only limits
+ * are that a plane's pitch x rows stays under 2 GiB, and that I420 planes more than 2 GiB apart take a slower path.
+ * Only the row bytes of every row are used as pixels, but the kernels fetch whole 16-byte chunks: every row must be
+ * readable up to its row bytes rounded up to 16 (which its pitch covers). What lies in the padding, between the
+ * planes or around a window never reaches the output. */
 typedef struct evam_image {
     int32_t fourcc;
     int32_t width;

@@ -43,8 +43,9 @@ def expected(O, frame, quality):
     return jpeg_ref.encode(O.np_to_bgr(frame, 0, 0, frame.width, frame.height), quality)
 
 
-def check(evam, O, gpu, pp, frames, quality, what):
-    files = pp.encode_jpeg(upload(evam, frames, gpu), quality)
+def check(evam, O, gpu, pp, frames, quality, what, imgs=None):
+    """``imgs``: the device images of ``frames`` where the caller placed them itself (default: one upload per plane)."""
+    files = pp.encode_jpeg(imgs or upload(evam, frames, gpu), quality)
     assert pp.stats().kernels & evam.native.KERNEL_JPEG
     assert len(files) == len(frames)
     for i, (f, got) in enumerate(zip(frames, files)):
