@@ -15,8 +15,8 @@ letterbox / central-crop resize -> ROI crop-resize -> normalisation -> NCHW (pla
 import sys as _sys
 
 from ._native import PreProcError, jpeg_bound, jpeg_header, load_library  # noqa: F401
-from .preproc import (HipPreProcessor, Image, ImageBatch, PreProcInfo, Roi, RoiBatch, Transform,  # noqa: F401
-                      create_preprocessor, output_dtype, plane_layout, tensor_layout)
+from .preproc import (DeviceRoiList, HipPreProcessor, Image, ImageBatch, PreProcInfo, Roi, RoiBatch,  # noqa: F401
+                      Transform, create_preprocessor, output_dtype, plane_layout, tensor_layout)
 from . import _native as native  # noqa: F401
 from . import streams  # noqa: F401
 from . import postproc  # noqa: F401

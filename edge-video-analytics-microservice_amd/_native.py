@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = (
     "evam_pp_get_stats", "evam_pp_destroy", "evam_pp_last_error", "evam_pp_abi_version",
     "evam_pp_linear_table", "evam_pp_norm_table",
     "evam_pp_jpeg_header", "evam_pp_encode_jpeg",
+    "evam_pp_ssd_rois", "evam_pp_ssd_rois_host", "evam_pp_run_device_rois",
 )
 # ... and the one that returns size_t (tests/test_abi.py reads the header's int / void / const char* declarations)
 EXPORTED_SYMBOLS_SIZE_T = ("evam_pp_jpeg_bound",)
@@ -89,6 +90,12 @@ class EvamTransform(ctypes.Structure):
                 ("resized_w", c_i32), ("resized_h", c_i32)]
 
 
+class EvamRoiList(ctypes.Structure):
+    """``evam_roi_list``: a ROI list in device memory (host memory for ``evam_pp_ssd_rois_host``)."""
+
+    _fields_ = [("rois", ctypes.c_void_p), ("count", ctypes.c_void_p), ("cap", c_i32), ("reserved", c_i32)]
+
+
 class EvamStats(ctypes.Structure):
     _fields_ = [("src_bytes", ctypes.c_int64), ("dst_bytes", ctypes.c_int64), ("n_items", c_i32),
                 ("n_launches", c_i32), ("last_kernel_ms", ctypes.c_float), ("kernels", ctypes.c_uint32)]
@@ -102,7 +109,8 @@ KERNEL_JPEG = 128
 JPEG_HEADER_LEN = 623  # SOI .. SOS of every file evam_pp_encode_jpeg writes
 
 
-STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32}
+STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32,
+                EvamRoiList: 24}
 
 _LIB = None
 
@@ -144,6 +152,17 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_jpeg_bound.restype = ctypes.c_size_t
     lib.evam_pp_encode_jpeg.argtypes = [vp, P(EvamImage), ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]
     lib.evam_pp_encode_jpeg.restype = ctypes.c_int
+    if not hasattr(lib, "evam_pp_ssd_rois"):  # an A/B variant built before the device-list calls (EVAM_PP_LIB)
+        return lib
+    ssd = [vp, ctypes.c_int, ctypes.c_int, P(EvamImage), P(EvamTransform), ctypes.c_int, ctypes.c_int, ctypes.c_float,
+           P(c_i32), ctypes.c_int, P(EvamRoiList)]
+    lib.evam_pp_ssd_rois.argtypes = [vp] + ssd
+    lib.evam_pp_ssd_rois.restype = ctypes.c_int
+    lib.evam_pp_ssd_rois_host.argtypes = ssd
+    lib.evam_pp_ssd_rois_host.restype = ctypes.c_int
+    lib.evam_pp_run_device_rois.argtypes = [vp, P(EvamImage), ctypes.c_int, P(EvamRoiList), P(EvamPreproc),
+                                            P(EvamTensor), vp]
+    lib.evam_pp_run_device_rois.restype = ctypes.c_int
     return lib
 
 
@@ -192,6 +211,59 @@ def jpeg_bound(width: int, height: int) -> int:
     if n == 0:
         raise PreProcError(ERR_INVALID_ARG, f"jpeg_bound: bad frame size {width}x{height}")
     return n
+
+
+def transforms_array(transforms, n: int):
+    """``evam_transform[n]`` of a sequence of transforms (objects with the struct's fields), or None for None (every
+    item a plain full-frame resize). A ctypes array of EvamTransform passes through."""
+    if transforms is None:
+        return None
+    if isinstance(transforms, ctypes.Array) and transforms._type_ is EvamTransform:
+        arr = transforms
+    else:
+        raw = getattr(transforms, "_xf", None)  # preproc.Transforms: the array evam_pp_run filled
+        if isinstance(raw, ctypes.Array) and raw._type_ is EvamTransform:
+            arr = raw
+        else:
+            arr = (EvamTransform * len(transforms))()
+            for i, t in enumerate(transforms):
+                a = arr[i]
+                a.scale_x, a.scale_y = t.scale_x, t.scale_y
+                a.crop_x, a.crop_y, a.crop_w, a.crop_h = t.crop_x, t.crop_y, t.crop_w, t.crop_h
+                a.pad_x, a.pad_y, a.resized_w, a.resized_h = t.pad_x, t.pad_y, t.resized_w, t.resized_h
+    if len(arr) != n:
+        raise PreProcError(ERR_INVALID_ARG, f"{len(arr)} transforms for {n} items")
+    return arr
+
+
+def ssd_rois_host(det, sizes, transforms, tensor_size, threshold: float, labels=None, cap: int | None = None):
+    """``evam_pp_ssd_rois_host``: the rects a gvaclassify stage crops from an SSD output, on the host.
+
+    ``det``: float32 ``[n, K, 7]``; ``sizes``: ``(width, height)`` of every item's frame; ``transforms``: None or one
+    per item; ``tensor_size``: ``(W, H)`` of the detector's input; ``labels``: accepted label ids or None.
+    Returns ``(int32 [min(count, cap), 5] rows of (src_index, x, y, w, h), count)``. Host-only."""
+    import numpy as np
+
+    lib = load_library()
+    a = np.ascontiguousarray(det, dtype=np.float32)
+    a = a.reshape(a.shape[0], -1, 7)
+    n, k = int(a.shape[0]), int(a.shape[1])
+    if len(sizes) != n:
+        raise PreProcError(ERR_INVALID_ARG, f"{len(sizes)} frame sizes for {n} items")
+    srcs = (EvamImage * max(n, 1))()
+    for i, (w, h) in enumerate(sizes):
+        srcs[i].width, srcs[i].height = int(w), int(h)
+    xf = transforms_array(transforms, n)
+    cap = n * k if cap is None else int(cap)
+    rois = np.full((max(cap, 1), 5), -1, np.int32)
+    count = ctypes.c_uint32(0)
+    lab = None if labels is None else np.ascontiguousarray(list(labels), dtype=np.int32)
+    lst = EvamRoiList(rois.ctypes.data, ctypes.addressof(count), cap, 0)
+    check(lib, lib.evam_pp_ssd_rois_host(
+        a.ctypes.data, n, k, srcs, xf, int(tensor_size[0]), int(tensor_size[1]), float(threshold),
+        None if lab is None else lab.ctypes.data_as(ctypes.POINTER(c_i32)), 0 if lab is None else int(lab.size),
+        ctypes.byref(lst)))
+    return rois[:min(int(count.value), cap)].copy(), int(count.value)
 
 
 class PreProcError(RuntimeError):

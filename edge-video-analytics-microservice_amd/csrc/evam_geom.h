@@ -116,6 +116,70 @@ EVAM_HD inline int roi_geometry(int f, int W, int H, bool has_roi, int rx, int r
     return 0;
 }
 
+// One SSD DetectionOutput row (image_id, label, conf, x0, y0, x1, y1) of an item -> the frame rect a gvaclassify
+// stage crops, or false when the host path would drop the row. Restates the Python path operation by operation, in
+// double, in its order (postproc.parse_ssd_batch's `conf >= threshold` is a float32 comparison, as numpy does it):
+//   is_identity; tensor_box_to_frame (identity items clip the box, others map it through the transform and divide by
+//   the frame size); roi_rect (floor(v * W + 0.5)); pipeline_server.roi_inside; the label filter on int(label).
+// xf == NULL: a plain full-frame resize. labels == NULL: every label. A row with a non-finite box value (or, with a
+// label list, a label that is not finite or outside int32) is rejected. The caller handles the image_id terminator.
+EVAM_HD inline bool ssd_row_rect(const float* row, const evam_transform* xf, int W, int H, int TW, int TH,
+                                 float threshold, const int32_t* labels, int n_labels, int& rx, int& ry, int& rw,
+                                 int& rh) {
+    if (!(row[2] >= threshold)) return false;
+    double b[4];
+    for (int j = 0; j < 4; j++) {
+        const float v = row[3 + j];
+        if (!(v - v == 0.f)) return false;  // inf or NaN
+        b[j] = (double)v;
+    }
+    if (labels) {
+        const float lf = row[1];
+        if (!(lf - lf == 0.f) || lf >= 2147483648.f || lf < -2147483648.f) return false;
+        const int32_t id = (int32_t)lf;  // int(label): truncation
+        bool hit = false;
+        for (int j = 0; j < n_labels; j++) hit |= labels[j] == id;
+        if (!hit) return false;
+    }
+    const bool identity = !xf || (xf->pad_x == 0 && xf->pad_y == 0 && xf->crop_x == 0 && xf->crop_y == 0 &&
+                                  xf->crop_w == W && xf->crop_h == H && xf->resized_w == TW && xf->resized_h == TH);
+    if (!identity) {
+        const double sx = (double)xf->scale_x, sy = (double)xf->scale_y;
+        for (int j = 0; j < 4; j++) {
+            double v;
+            if ((j & 1) == 0) {
+                v = b[j] * (double)TW;
+                v = v - (double)xf->pad_x;
+                v = v / sx;
+                v = v + (double)xf->crop_x;
+                v = v / (double)W;
+            } else {
+                v = b[j] * (double)TH;
+                v = v - (double)xf->pad_y;
+                v = v / sy;
+                v = v + (double)xf->crop_y;
+                v = v / (double)H;
+            }
+            if (!(v - v == 0.)) return false;  // a zero scale: the host path raises
+            b[j] = v;
+        }
+    }
+    for (int j = 0; j < 4; j++) {
+        double v = b[j];
+        v = 0.0 > v ? 0.0 : v;  // max(v, 0.0), then min(.., 1.0)
+        v = 1.0 < v ? 1.0 : v;
+        b[j] = v;
+    }
+    const double fx = floor(b[0] * (double)W + 0.5), fy = floor(b[1] * (double)H + 0.5);
+    const double fw = floor((b[2] - b[0]) * (double)W + 0.5), fh = floor((b[3] - b[1]) * (double)H + 0.5);
+    const int x = (int)fx, y = (int)fy, w = (int)fw, h = (int)fh;  // |values| <= frame size + 1
+    if (w <= 0 || h <= 0) return false;
+    const int xe = x + w < W ? x + w : W, ye = y + h < H ? y + h : H;
+    if (xe - (x > 0 ? x : 0) <= 0 || ye - (y > 0 ? y : 0) <= 0) return false;
+    rx = x; ry = y; rw = w; rh = h;
+    return true;
+}
+
 // 16-byte-aligned byte windows [fs, fs + 16 n) of a luma / packed row (Y) and of a chroma row (C) that
 // the taps of source columns [xa, xb] (absolute) read.
 EVAM_HD inline void footprint_chunks(int FMT, int bpp, int xa, int xb, int& fsY, int& nY, int& fsC, int& nC) {

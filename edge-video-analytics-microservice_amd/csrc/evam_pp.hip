@@ -2743,7 +2743,11 @@ __device__ __forceinline__ void wait_vmcnt_stores(int nk) {
 // 7 resident workgroups per CU need <= 96 SGPRs (800 / (96 + 16)); the occupancy API does not count
 // SGPRs (MI355X_MICROARCH.md, Residency): uncapped, the kernel's ~106 allowed only 6 and a 1,600-ROI
 // batch ran a second round (profiles/r02r_c3_roi_timeline_before.json).
-template <int FMT, int OUT, int PX, int NB>
+// DEV (evam_pp_run_device_rois): the records were written by evam_pp_roi_records from a device-resident ROI list, one
+// per (list entry, row tile) of the list's capacity; a record with an empty row range (an entry past the list's count,
+// or an invalid one) ends its workgroup before any DMA is issued. A sibling instantiation: DEV = false compiles to the
+// code it had before the parameter existed.
+template <int FMT, int OUT, int PX, int NB, bool DEV = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void evam_pp_roi(const QParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     static_assert(NB == 2, "two staging buffers (three were retired in round 5)");
@@ -2766,6 +2770,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
     // not map device memory (~1-2 us more under load). Its latency overlaps the LUT load below.
     typedef unsigned int u32x16 __attribute__((ext_vector_type(16)));
     const u32x16 rec = *((const __attribute__((address_space(4))) u32x16*)(P.recs) + blockIdx.x);
+    if constexpr (DEV) {
+        if ((rec[15] >> 16) <= (rec[15] & 0xFFFF)) return;  // no rows: nothing issued yet, the LDS is untouched
+    }
     // The LUT by LDS-DMA, issued first: no VGPR waits on it, and group 0's wait (everything older than its
     // DMA) covers it. Loaded into registers and stored it held the row-table barrier, and so the first DMA,
     // up to ~15 us for the last workgroups behind the chip's first DMA burst (profiles/r03l_c3_roi_timeline.json).
@@ -3066,6 +3073,145 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
         asm volatile("" ::: "memory");
     }
     EVAM_STAMP(3);
+}
+
+// ------------------------------------------------------------------------------------------------
+// device-resident ROI lists (evam_pp_ssd_rois, evam_pp_run_device_rois)
+// ------------------------------------------------------------------------------------------------
+// Records kernel: one thread per (list entry, row tile) of the list's capacity writes that unit's RoiRec, in list
+// order, from the entry and the per-source table (RecFrame per source: the frame half of a record). An entry past
+// min(*count, cap), with a src_index outside the sources, or whose rect clips to nothing (roi_clip, the host's own
+// rule) gets the row range [0, 0): evam_pp_roi<.., DEV = true> returns on it. Ordinary vector stores: the ROI kernel
+// launched next on the stream sees them through the kernel boundary.
+struct DParams {
+    const evam_roi* rois;
+    const uint32_t* count;
+    const uint4* srcs;  // [n_srcs][3]
+    RoiRec* recs;       // [cap * tiles]
+    int32_t* status;    // NULL or [cap]
+    int cap, n_srcs, tiles, TH, DH, fmt;
+};
+
+__global__ __launch_bounds__(kThreads) void evam_pp_roi_records(const DParams P) {
+    const int u = blockIdx.x * kThreads + threadIdx.x;
+    if (u >= P.cap * P.tiles) return;
+    const int e = u / P.tiles, t = u - e * P.tiles;
+    const uint32_t cnt = *P.count;
+    bool live = (uint32_t)e < cnt;  // e < cap by the grid
+    int st = 0;
+    uint4 l0 = {0u, 0u, 0u, 0u}, l1 = l0, l2 = l0;
+    int rx = 0, ry = 0, rw = 0, rh = 0;
+    if (live) {
+        const int32_t* r = reinterpret_cast<const int32_t*>(P.rois + e);
+        const int si = r[0];
+        rx = r[1]; ry = r[2]; rw = r[3]; rh = r[4];
+        if ((unsigned)si >= (unsigned)P.n_srcs) {
+            st = EVAM_PP_ERR_INVALID_ARG;
+            live = false;
+        } else {
+            l0 = P.srcs[3 * si];
+            l1 = P.srcs[3 * si + 1];
+            l2 = P.srcs[3 * si + 2];  // pitch[2], width | height << 16, 0, 0
+            Geom g;
+            if (roi_clip(P.fmt, (int)(l2.y & 0xFFFF), (int)(l2.y >> 16), true, rx, ry, rw, rh, g)) {
+                st = EVAM_PP_ERR_EMPTY_ROI;
+                live = false;
+            }
+        }
+    }
+    const uint32_t row0 = live ? (uint32_t)(t * P.TH) : 0u;
+    const uint32_t row1 = live ? (uint32_t)min(P.DH, (t + 1) * P.TH) : 0u;
+    uint4* o = reinterpret_cast<uint4*>(P.recs + u);
+    o[0] = l0;
+    o[1] = l1;
+    o[2] = make_uint4(l2.x, l2.y, (uint32_t)rx, (uint32_t)ry);
+    o[3] = make_uint4((uint32_t)rw, (uint32_t)rh, (uint32_t)e, row0 | (row1 << 16));
+    if (t == 0 && P.status) P.status[e] = st;
+}
+
+// SSD rows -> ROI list, an ordered compaction in three launches: evam_pp_ssd_rows<false> counts the accepted rows
+// of every item (one workgroup per item), evam_pp_ssd_scan turns the counts into each item's first list position and
+// the total, evam_pp_ssd_rows<true> evaluates the rows again and writes every accepted rect at its position: item
+// order, then row order, as the host path lists them. ssd_row_rect (evam_geom.h) is the host's arithmetic.
+struct SsdParams {
+    const float* det;          // [n_items][k][7]
+    const int2* sizes;         // per item: its frame's (width, height)
+    const evam_transform* xf;  // per item, or NULL: identity
+    const int32_t* labels;     // accepted label ids, or NULL: all
+    uint32_t* item_count;      // [n_items]
+    uint32_t* item_off;        // [n_items]
+    evam_roi* rois;
+    uint32_t* count;
+    int n_items, k, n_labels, TW, TH, cap;
+    float threshold;
+};
+
+template <bool EMIT>
+__global__ __launch_bounds__(kThreads) void evam_pp_ssd_rows(const SsdParams P) {
+    __shared__ int s_end;
+    __shared__ uint32_t s_w[kThreads / 64];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* d = P.det + (size_t)i * (size_t)P.k * 7;
+    if (tid == 0) s_end = P.k;
+    __syncthreads();
+    // the rows before the first image_id < 0
+    for (int r = tid; r < P.k; r += kThreads)
+        if (d[(size_t)r * 7] < 0.f) {
+            atomicMin(&s_end, r);
+            break;
+        }
+    __syncthreads();
+    const int kend = s_end;
+    const int2 wh = P.sizes[i];
+    const evam_transform* xf = P.xf ? P.xf + i : nullptr;
+    const uint32_t base = EMIT ? P.item_off[i] : 0u;
+    uint32_t total = 0;
+    for (int r0 = 0; r0 < kend; r0 += kThreads) {  // kend is uniform: every thread takes every barrier
+        const int r = r0 + tid;
+        int x = 0, y = 0, w = 0, h = 0;
+        const bool acc = r < kend && ssd_row_rect(d + (size_t)r * 7, xf, wh.x, wh.y, P.TW, P.TH, P.threshold, P.labels,
+                                                  P.n_labels, x, y, w, h);
+        const unsigned long long m = __ballot(acc);
+        if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (int v = 0; v < kThreads / 64; v++) {
+            before += v < wave ? s_w[v] : 0u;
+            all += s_w[v];
+        }
+        if (EMIT && acc) {
+            const uint32_t pos = base + total + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (pos < (uint32_t)P.cap) {
+                int32_t* o = reinterpret_cast<int32_t*>(P.rois + pos);
+                o[0] = i; o[1] = x; o[2] = y; o[3] = w; o[4] = h;
+            }
+        }
+        total += all;
+        __syncthreads();  // s_w is rewritten by the next chunk
+    }
+    if (!EMIT && tid == 0) P.item_count[i] = total;
+}
+
+__global__ __launch_bounds__(kThreads) void evam_pp_ssd_scan(const uint32_t* cnt, uint32_t* off, int n, uint32_t* total) {
+    __shared__ uint32_t s[kThreads];
+    const int tid = threadIdx.x;
+    uint32_t running = 0;
+    for (int i0 = 0; i0 < n; i0 += kThreads) {
+        const int i = i0 + tid;
+        const uint32_t v = i < n ? cnt[i] : 0u;
+        s[tid] = v;
+        __syncthreads();
+        for (int d = 1; d < kThreads; d <<= 1) {  // inclusive scan of the chunk
+            const uint32_t a = tid >= d ? s[tid - d] : 0u;
+            __syncthreads();
+            s[tid] += a;
+            __syncthreads();
+        }
+        if (i < n) off[i] = running + s[tid] - v;
+        running += s[kThreads - 1];
+        __syncthreads();
+    }
+    if (tid == 0) *total = running;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3435,6 +3581,52 @@ hipError_t launch_roi_t(int px, int nb, const QParams& p, int grid, int lds, hip
     if (px == 4 && p.DW % 4 == 0) return launch_roi_px<FMT, OUT, 4, 2>(p, grid, lds, s);
     if (px == 2 && p.DW % 2 == 0) return launch_roi_px<FMT, OUT, 2, 2>(p, grid, lds, s);
     return launch_roi_px<FMT, OUT, 1, 2>(p, grid, lds, s);
+}
+
+// The device-list siblings (DEV = true): PX = 2, or 1 for odd output widths (EVAM_PP_ROI_PX = 4 is not built for them).
+template <int FMT, int OUT, int PX>
+hipError_t launch_roi_dev_px(const QParams& p, int grid, int lds, hipStream_t s) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)evam_pp_roi<FMT, OUT, PX, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((evam_pp_roi<FMT, OUT, PX, 2, true>), dim3(grid), dim3(kThreads), lds, s, p);
+    return hipGetLastError();
+}
+constexpr int roi_dev_px(int px, int DW) { return (px == 2 || px == 4) && DW % 2 == 0 ? 2 : 1; }
+template <int FMT>
+hipError_t launch_roi_dev_t(int out, int px, const QParams& p, int grid, int lds, hipStream_t s) {
+    const int k = out_kind(out), pxv = roi_dev_px(px, p.DW);
+    if (pxv == 2)
+        return k == 0 ? launch_roi_dev_px<FMT, 0, 2>(p, grid, lds, s)
+             : k == 1 ? launch_roi_dev_px<FMT, 1, 2>(p, grid, lds, s) : launch_roi_dev_px<FMT, 2, 2>(p, grid, lds, s);
+    return k == 0 ? launch_roi_dev_px<FMT, 0, 1>(p, grid, lds, s)
+         : k == 1 ? launch_roi_dev_px<FMT, 1, 1>(p, grid, lds, s) : launch_roi_dev_px<FMT, 2, 1>(p, grid, lds, s);
+}
+hipError_t launch_roi_dev(int f, int out, int px, const QParams& p, int grid, int lds, hipStream_t s) {
+    switch (f) {
+    case kNV12: return launch_roi_dev_t<kNV12>(out, px, p, grid, lds, s);
+    case kI420: return launch_roi_dev_t<kI420>(out, px, p, grid, lds, s);
+    case kBGRX: return launch_roi_dev_t<kBGRX>(out, px, p, grid, lds, s);
+    default: return launch_roi_dev_t<kBGR>(out, px, p, grid, lds, s);
+    }
+}
+template <int FMT>
+const void* roi_dev_fn_t(int k, int pxv) {
+    if (pxv == 2)
+        return k == 0 ? (const void*)evam_pp_roi<FMT, 0, 2, 2, true>
+             : k == 1 ? (const void*)evam_pp_roi<FMT, 1, 2, 2, true> : (const void*)evam_pp_roi<FMT, 2, 2, 2, true>;
+    return k == 0 ? (const void*)evam_pp_roi<FMT, 0, 1, 2, true>
+         : k == 1 ? (const void*)evam_pp_roi<FMT, 1, 1, 2, true> : (const void*)evam_pp_roi<FMT, 2, 1, 2, true>;
+}
+const void* roi_dev_fn(int f, int out, int pxv) {
+    const int k = out_kind(out);
+    switch (f) {
+    case kNV12: return roi_dev_fn_t<kNV12>(k, pxv);
+    case kI420: return roi_dev_fn_t<kI420>(k, pxv);
+    case kBGRX: return roi_dev_fn_t<kBGRX>(k, pxv);
+    default: return roi_dev_fn_t<kBGR>(k, pxv);
+    }
 }
 
 hipError_t launch_roi(int f, int out, int px, int nb, const QParams& p, int grid, int lds, hipStream_t s) {
@@ -3970,7 +4162,7 @@ const void* roi_fn(int f, int out, int px, int nb) {
 // 12 KB (EVAM_PP_ROI_BUF fixes it). `slots`: workgroups resident at once with that carve.
 constexpr int kRoiWavesPerSimd = 7;  // evam_pp_roi<*, *, 1> at kRoiK = 6: <= 72 VGPRs
 bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, int count, int n_cu, const Knobs& kn,
-              QParams& q, int& base_tiles, int& lds, int64_t& slots) {
+              QParams& q, int& base_tiles, int& lds, int64_t& slots, bool dev = false) {
     if (DW > kRoiK * kThreads || DH > 65535) return false;
     q.DW = DW; q.DH = DH;
     q.TH = (int64_t)DW * DH <= 32768 ? DH : std::max(8, std::min(DH, 16384 / DW));
@@ -3981,7 +4173,7 @@ bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, i
     q.offBuf = q.offYT + (int)sizeof(YTab) * q.TH;
     const int64_t grid = (int64_t)count * base_tiles;
     const int per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(kRoiWavesPerSimd, (grid + n_cu - 1) / n_cu));
-    const int pxv = (px == 4 || px == 2) && DW % px == 0 ? px : 1;
+    const int pxv = dev ? roi_dev_px(px, DW) : ((px == 4 || px == 2) && DW % px == 0 ? px : 1);
     const uint32_t qw = (uint32_t)(DW / pxv);
     q.mqw = qw > 1 ? (uint32_t)((0x100000000ull + qw - 1) / qw) : 0u;
     const int nb = 2;
@@ -3990,7 +4182,7 @@ bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, i
     q.buf_bytes = (std::max(buf, max_row_bytes) + 15) & ~15;
     lds = q.offBuf + nb * q.buf_bytes;
     if (q.buf_bytes > 32 * 1024 || lds > 160 * 1024) return false;
-    const void* fn = roi_fn(f, out_dtype, pxv, nb);
+    const void* fn = dev ? roi_dev_fn(f, out_dtype, pxv) : roi_fn(f, out_dtype, pxv, nb);
     int res = resident_per_cu(fn, lds);
     while (kn.roi_buf <= 0 && res < per_cu && q.buf_bytes - 512 >= max_row_bytes) {
         q.buf_bytes -= 512;
@@ -4138,6 +4330,16 @@ struct evam_pp {
     int nhwc_key[4][16] = {};      // per format: what the last interleaved uniform group's choice depended on
     int nhwc_ok[4] = {-1, -1, -1, -1};  // ... and the choice: 1 strip / wave kernel, 0 generic kernel (-1: none yet)
     JpegScratch jpeg;              // evam_pp_encode_jpeg: device scratch and the tables' key
+    // Device-resident ROI lists. Both buffers are written and read by kernels only, all on the handle's stream, so
+    // stream order makes their reuse safe with any number of calls in flight (evam_pp_set_stream orders a new stream
+    // behind the old one); they grow by hipFree + hipMalloc, and hipFree waits for the kernels that still use them.
+    void* dev_recs = nullptr;      // evam_pp_run_device_rois: RoiRec x cap x tiles
+    size_t dev_recs_cap = 0;
+    void* dev_cnt = nullptr;       // evam_pp_ssd_rois: per-item counts, then per-item list offsets
+    size_t dev_cnt_cap = 0;
+    std::vector<uint8_t> h_aux;    // their host-built block (per-source table / per-item sizes, transforms, labels)
+    DescRing ring_ssd;             // evam_pp_ssd_rois' block: a ring of its own, so that a detect -> classify chain that
+                                   // alternates it with evam_pp_run_device_rois' block re-uploads neither when unchanged
 };
 
 namespace {
@@ -4224,15 +4426,19 @@ void evam_pp_destroy(evam_pp* h) {
     }
 #endif
     (void)hipSetDevice(h->device);
-    if (h->ring.have_copy || h->pin.cur >= 0) {
+    if (h->ring.have_copy || h->ring_ssd.have_copy || h->pin.cur >= 0) {
         (void)hipStreamSynchronize(h->stream);
         if (h->ring.have_copy) (void)hipStreamSynchronize(h->ring.copy);
+        if (h->ring_ssd.have_copy) (void)hipStreamSynchronize(h->ring_ssd.copy);
     }
     HipRings b;
     h->ring.release(b);
+    h->ring_ssd.release(b);
     h->pin.release(b);
     for (void* p : h->jpeg.buf)
         if (p) (void)hipFree(p);  // waits for kernels that still use it
+    if (h->dev_recs) (void)hipFree(h->dev_recs);
+    if (h->dev_cnt) (void)hipFree(h->dev_cnt);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -4242,7 +4448,7 @@ void evam_pp_destroy(evam_pp* h) {
 int evam_pp_set_stream(evam_pp* h, void* hip_stream) {
     if (!h) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_set_stream: NULL handle");
     hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-    if (ns != h->stream && (h->ring.cur >= 0 || h->pin.cur >= 0)) {
+    if (ns != h->stream && (h->ring.cur >= 0 || h->pin.cur >= 0 || h->ring_ssd.cur >= 0)) {
         // Order the new stream behind everything already launched on the old one, so the descriptor
         // slots' fences (recorded on the current stream) keep covering earlier kernels.
         HIP_TRY(hipSetDevice(h->device));
@@ -4312,6 +4518,64 @@ int evam_pp_norm_table(const evam_preproc* cfg, void* out) {
 
 namespace {
 
+// The sources of a call: format, size, plane pointers and pitches.
+int validate_sources(const evam_image* srcs, int n_srcs) {
+    for (int i = 0; i < n_srcs; i++) {
+        const evam_image& s = srcs[i];
+        const int f = fmt_id(s.fourcc);
+        if (f < 0) return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_run: srcs[%d] fourcc 0x%08x unsupported", i, s.fourcc);
+        if (s.width <= 0 || s.height <= 0 || s.width > 32768 || s.height > 32768)
+            return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] bad size %dx%d", i, s.width, s.height);
+        if ((f == kNV12 || f == kI420) && ((s.width | s.height) & 1))
+            return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] 4:2:0 frame must have even size (%dx%d)", i, s.width, s.height);
+        for (int p = 0; p < fmt_nplanes(f); p++) {
+            const int row_bytes = p == 0 ? s.width * fmt_bpp(f) : (f == kNV12 ? s.width : s.width / 2);
+            const int rows = p == 0 ? s.height : s.height / 2;
+            if (!s.planes[p]) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d].planes[%d] is NULL", i, p);
+            if (((uintptr_t)s.planes[p] & 15) || (s.pitch[p] & 15))
+                return fail(EVAM_PP_ERR_ALIGNMENT, "evam_pp_run: srcs[%d] plane %d pointer/pitch (%d) not 16-byte aligned", i, p, s.pitch[p]);
+            if (s.pitch[p] < row_bytes)
+                return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] plane %d pitch %d < row bytes %d", i, p, s.pitch[p], row_bytes);
+            // the kernels address a plane through buffer resources with 32-bit byte offsets
+            if ((int64_t)s.pitch[p] * rows > INT32_MAX)
+                return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] plane %d (%d x %d B) exceeds 2 GiB", i, p, rows, s.pitch[p]);
+        }
+    }
+    return 0;
+}
+
+// The first kLutBytes of a call's descriptor block: the normalisation table of cfg (zeros for u8 output), from the
+// handle's cached copy.
+void block_lut(evam_pp* h, const evam_preproc* cfg, uint8_t* blk) {
+    if (cfg->out_dtype == EVAM_DTYPE_U8) {
+        memset(blk, 0, kLutBytes);
+        return;
+    }
+    // The LUT depends only on the dtype and the normalisation fields: rebuilt when they change.
+    evam_preproc key{};
+    key.out_dtype = cfg->out_dtype;
+    key.norm_flags = cfg->norm_flags;
+    memcpy(key.range, cfg->range, sizeof(key.range));
+    memcpy(key.mean, cfg->mean, sizeof(key.mean));
+    memcpy(key.std, cfg->std, sizeof(key.std));
+    if (!h->lut_valid || memcmp(&key, &h->lut_key, sizeof(key)) != 0) {
+        if (cfg->out_dtype == EVAM_DTYPE_F16 || cfg->out_dtype == EVAM_DTYPE_BF16) {
+            // norm_table's 16-bit elements, one per 4-byte entry (low half; the kernels read only that)
+            uint16_t t16[768];
+            norm_table(*cfg, t16);
+            for (int i = 0; i < 768; i++) {
+                const uint32_t b = t16[i];
+                memcpy(&h->lut[i], &b, 4);
+            }
+        } else {
+            norm_table(*cfg, h->lut);
+        }
+        h->lut_key = key;
+        h->lut_valid = true;
+    }
+    memcpy(blk, h->lut, kLutBytes);
+}
+
 // evam_pp_run and evam_pp_run_slots. slots == NULL: item i -> slot dst->slot_offset + i * dst->slot_stride; else item i
 // -> slot slots[i]. The kernels read one output index per item (ItemArg / ItemDesc .index, RoiRec .item) and compute
 // slot = slot_offset + index * slot_stride, so an explicit table travels as index = slots[i], offset 0, stride 1.
@@ -4353,28 +4617,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         return fail(EVAM_PP_ERR_ALIGNMENT, "evam_pp_run: dst->data is not aligned to its %d-byte elements", esz);
     const Knobs& kn = h->knobs;
 
-    // ---- validate sources ----
-    for (int i = 0; i < n_srcs; i++) {
-        const evam_image& s = srcs[i];
-        const int f = fmt_id(s.fourcc);
-        if (f < 0) return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_run: srcs[%d] fourcc 0x%08x unsupported", i, s.fourcc);
-        if (s.width <= 0 || s.height <= 0 || s.width > 32768 || s.height > 32768)
-            return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] bad size %dx%d", i, s.width, s.height);
-        if ((f == kNV12 || f == kI420) && ((s.width | s.height) & 1))
-            return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] 4:2:0 frame must have even size (%dx%d)", i, s.width, s.height);
-        for (int p = 0; p < fmt_nplanes(f); p++) {
-            const int row_bytes = p == 0 ? s.width * fmt_bpp(f) : (f == kNV12 ? s.width : s.width / 2);
-            const int rows = p == 0 ? s.height : s.height / 2;
-            if (!s.planes[p]) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d].planes[%d] is NULL", i, p);
-            if (((uintptr_t)s.planes[p] & 15) || (s.pitch[p] & 15))
-                return fail(EVAM_PP_ERR_ALIGNMENT, "evam_pp_run: srcs[%d] plane %d pointer/pitch (%d) not 16-byte aligned", i, p, s.pitch[p]);
-            if (s.pitch[p] < row_bytes)
-                return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] plane %d pitch %d < row bytes %d", i, p, s.pitch[p], row_bytes);
-            // the kernels address a plane through buffer resources with 32-bit byte offsets
-            if ((int64_t)s.pitch[p] * rows > INT32_MAX)
-                return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: srcs[%d] plane %d (%d x %d B) exceeds 2 GiB", i, p, rows, s.pitch[p]);
-        }
-    }
+    if (int rc = validate_sources(srcs, n_srcs)) return rc;
 
     HP(1);
     // ---- pass 1 (integer only): item -> source, format, clipped crop; validation ----
@@ -4624,33 +4867,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     }
     h->h_block.resize(nbytes);
     uint8_t* blk = h->h_block.data();
-    if (cfg->out_dtype != EVAM_DTYPE_U8) {
-        // The LUT depends only on the dtype and the normalisation fields: rebuilt when they change.
-        evam_preproc key{};
-        key.out_dtype = cfg->out_dtype;
-        key.norm_flags = cfg->norm_flags;
-        memcpy(key.range, cfg->range, sizeof(key.range));
-        memcpy(key.mean, cfg->mean, sizeof(key.mean));
-        memcpy(key.std, cfg->std, sizeof(key.std));
-        if (!h->lut_valid || memcmp(&key, &h->lut_key, sizeof(key)) != 0) {
-            if (half) {
-                // norm_table's 16-bit elements, one per 4-byte entry (low half; the kernels read only that)
-                uint16_t t16[768];
-                norm_table(*cfg, t16);
-                for (int i = 0; i < 768; i++) {
-                    const uint32_t b = t16[i];
-                    memcpy(&h->lut[i], &b, 4);
-                }
-            } else {
-                norm_table(*cfg, h->lut);
-            }
-            h->lut_key = key;
-            h->lut_valid = true;
-        }
-        memcpy(blk, h->lut, kLutBytes);
-    } else {
-        memset(blk, 0, kLutBytes);
-    }
+    block_lut(h, cfg, blk);
     int first[4] = {0, 0, 0, 0};
     {
         ItemDesc* desc = reinterpret_cast<ItemDesc*>(blk + desc_off);
@@ -5170,6 +5387,221 @@ int evam_pp_run_slots(evam_pp* h, const evam_image* srcs, int n_srcs, const evam
                       const evam_preproc* cfg, const evam_tensor* dst, const int32_t* slots, evam_transform* out_xform) {
     if (!slots) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run_slots: slots is NULL");
     return run_impl(h, srcs, n_srcs, items, n_items, cfg, dst, slots, out_xform);
+}
+
+}  // extern "C"
+
+// ---- device-resident ROI lists ----
+namespace {
+
+int grow_device(void** p, size_t* cap, size_t n, const char* who) {
+    if (*cap >= n) return 0;
+    if (*p) {
+        HIP_TRY(hipFree(*p));  // waits for the kernels that still use it
+        *p = nullptr;
+        *cap = 0;
+    }
+    const size_t c = std::max<size_t>(n * 2, 64 * 1024);
+    if (hipMalloc(p, c) != hipSuccess) {
+        *p = nullptr;
+        (void)hipGetLastError();
+        return fail(EVAM_PP_ERR_OOM, "%s: hipMalloc(%zu) failed", who, c);
+    }
+    *cap = c;
+    return 0;
+}
+
+int check_roi_list(const evam_roi_list* list, const char* who) {
+    if (!list || !list->rois || !list->count) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: NULL ROI list pointer", who);
+    if (list->cap <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: list cap %d must be > 0", who, list->cap);
+    return 0;
+}
+
+int check_ssd_args(const char* who, const float* det, int n_items, int k, const evam_image* srcs, int tensor_w,
+                   int tensor_h, const int32_t* labels, int n_labels, const evam_roi_list* list) {
+    if (!det || !srcs) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (int rc = check_roi_list(list, who)) return rc;
+    if (n_items <= 0 || k <= 0 || n_items > 65535 || k > 65535)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: n_items %d / k %d outside 1..65535", who, n_items, k);
+    if (tensor_w <= 0 || tensor_h <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad tensor size %dx%d", who, tensor_w, tensor_h);
+    if (n_labels < 0 || (!labels && n_labels > 0)) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad label list", who);
+    for (int i = 0; i < n_items; i++)
+        if (srcs[i].width <= 0 || srcs[i].height <= 0 || srcs[i].width > 32768 || srcs[i].height > 32768)
+            return fail(EVAM_PP_ERR_INVALID_ARG, "%s: srcs[%d] bad size %dx%d", who, i, srcs[i].width, srcs[i].height);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int evam_pp_ssd_rois_host(const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
+                          int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
+                          const evam_roi_list* list) {
+    if (int rc = check_ssd_args("evam_pp_ssd_rois_host", det, n_items, k, srcs, tensor_w, tensor_h, labels, n_labels, list))
+        return rc;
+    static const int32_t none = 0;
+    const int32_t* lab = labels ? (n_labels ? labels : &none) : nullptr;
+    uint32_t total = 0;
+    for (int i = 0; i < n_items; i++) {
+        const float* d = det + (size_t)i * (size_t)k * 7;
+        for (int r = 0; r < k; r++) {
+            const float* row = d + (size_t)r * 7;
+            if (row[0] < 0.f) break;
+            int x, y, w, h;
+            if (!ssd_row_rect(row, xf ? xf + i : nullptr, srcs[i].width, srcs[i].height, tensor_w, tensor_h, threshold, lab,
+                              n_labels, x, y, w, h))
+                continue;
+            if (total < (uint32_t)list->cap) list->rois[total] = evam_roi{i, x, y, w, h};
+            total++;
+        }
+    }
+    *list->count = total;
+    return EVAM_PP_OK;
+}
+
+int evam_pp_ssd_rois(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
+                     int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
+                     const evam_roi_list* list) {
+    if (!h) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_ssd_rois: NULL handle");
+    if (int rc = check_ssd_args("evam_pp_ssd_rois", det, n_items, k, srcs, tensor_w, tensor_h, labels, n_labels, list))
+        return rc;
+    // host block: [int2 x n_items: frame sizes][evam_transform x n_items, with xf][int32 x n_labels] (never empty)
+    const size_t off_xf = sizeof(int2) * (size_t)n_items;
+    const size_t off_lab = off_xf + (xf ? sizeof(evam_transform) * (size_t)n_items : 0);
+    std::vector<uint8_t>& blk = h->h_aux;
+    blk.assign(off_lab + sizeof(int32_t) * (size_t)std::max(1, n_labels), 0);
+    for (int i = 0; i < n_items; i++) {
+        const int32_t wh[2] = {srcs[i].width, srcs[i].height};
+        memcpy(blk.data() + sizeof(int2) * (size_t)i, wh, sizeof(wh));
+    }
+    if (xf) memcpy(blk.data() + off_xf, xf, sizeof(evam_transform) * (size_t)n_items);
+    if (n_labels) memcpy(blk.data() + off_lab, labels, sizeof(int32_t) * (size_t)n_labels);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = grow_device(&h->dev_cnt, &h->dev_cnt_cap, 2 * sizeof(uint32_t) * (size_t)n_items, "evam_pp_ssd_rois")) return rc;
+    const uint8_t* d_blk = nullptr;
+    {
+        HipRings b;
+        if (int rc = h->ring_ssd.upload(b, h->stream, blk.data(), blk.size(), &d_blk)) return rc;
+    }
+    SsdParams p{};
+    p.det = det;
+    p.sizes = reinterpret_cast<const int2*>(d_blk);
+    p.xf = xf ? reinterpret_cast<const evam_transform*>(d_blk + off_xf) : nullptr;
+    p.labels = labels ? reinterpret_cast<const int32_t*>(d_blk + off_lab) : nullptr;
+    p.item_count = static_cast<uint32_t*>(h->dev_cnt);
+    p.item_off = p.item_count + n_items;
+    p.rois = list->rois;
+    p.count = list->count;
+    p.n_items = n_items; p.k = k; p.n_labels = n_labels;
+    p.TW = tensor_w; p.TH = tensor_h; p.cap = list->cap;
+    p.threshold = threshold;
+    hipLaunchKernelGGL((evam_pp_ssd_rows<false>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
+    hipLaunchKernelGGL(evam_pp_ssd_scan, dim3(1), dim3(kThreads), 0, h->stream, p.item_count, p.item_off, n_items, p.count);
+    hipLaunchKernelGGL((evam_pp_ssd_rows<true>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "evam_pp_ssd_rois: kernel launch failed: %s", hipGetErrorString(e));
+    return EVAM_PP_OK;
+}
+
+int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi_list* list,
+                            const evam_preproc* cfg, const evam_tensor* dst, int32_t* status) {
+    const char* who = "evam_pp_run_device_rois";
+    if (!h || !srcs || !cfg || !dst) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (int rc = check_roi_list(list, who)) return rc;
+    if (n_srcs <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: n_srcs must be > 0", who);
+    if (!dst->data) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst->data is NULL", who);
+    if (dst->c != 3) return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: dst must have 3 channels (got %d)", who, dst->c);
+    if (dst->n <= 0 || dst->h <= 0 || dst->w <= 0)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad dst shape %dx%dx%dx%d", who, dst->n, dst->c, dst->h, dst->w);
+    if (cfg->out_dtype != EVAM_DTYPE_U8 && cfg->out_dtype != EVAM_DTYPE_F32 && cfg->out_dtype != EVAM_DTYPE_F16 &&
+        cfg->out_dtype != EVAM_DTYPE_BF16)
+        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: unknown out_dtype %d", who, cfg->out_dtype);
+    if (cfg->resize_mode < 0 || cfg->resize_mode > 2)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: unknown resize_mode %d", who, cfg->resize_mode);
+    if ((cfg->norm_flags & EVAM_NORM_MEAN_STD) && cfg->out_dtype != EVAM_DTYPE_U8)
+        for (int c = 0; c < 3; c++)
+            if (cfg->std[c] == 0.f) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: std[%d] == 0", who, c);
+    const int DW = dst->w, DH = dst->h, cap = list->cap;
+    const int64_t plane = (int64_t)DW * DH;
+    const int esz = out_esz(out_kind(cfg->out_dtype));
+    if (plane * 3 * (int64_t)dst->n > ((int64_t)1 << 40)) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst too large", who);
+    if (plane * esz > INT32_MAX) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst plane %dx%d exceeds 2 GiB", who, DW, DH);
+    if (dst->layout == EVAM_LAYOUT_NHWC)
+        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: interleaved (NHWC) output is not served from a device list", who);
+    if (dst->layout != EVAM_LAYOUT_NCHW) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: unknown dst layout %d", who, dst->layout);
+    for (int i : {0, cap - 1}) {  // slots are linear in the entry index: the first and the last bound them all
+        const int64_t slot = (int64_t)dst->slot_offset + (int64_t)i * dst->slot_stride;
+        if (slot < 0 || slot >= dst->n)
+            return fail(EVAM_PP_ERR_INVALID_ARG, "%s: entry %d -> slot %lld outside tensor batch %d", who, i, (long long)slot, dst->n);
+    }
+    if (int rc = validate_sources(srcs, n_srcs)) return rc;
+    const int f = fmt_id(srcs[0].fourcc);
+    int max_w = 0;
+    for (int i = 0; i < n_srcs; i++) {
+        if (fmt_id(srcs[i].fourcc) != f)
+            return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: sources of more than one format in a call (srcs[%d])", who, i);
+        max_w = std::max(max_w, srcs[i].width);
+    }
+    // Planned without the rects: staging for the widest source, occupancy from the list's capacity, units in list order.
+    const Knobs& kn = h->knobs;
+    QParams q{};
+    int base = 1, lds = 0;
+    int64_t slots = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if (!plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_w), cap, h->n_cu, kn, q, base, lds, slots, true))
+        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: %dx%d output from %d-wide sources is not planned by the ROI kernel", who, DW,
+                    DH, max_w);
+    const int64_t units = (int64_t)cap * base;
+    if (units > 0x7FFFFFFF - kThreads) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: too many tiles", who);
+    // host block: [LUT][RecFrame x n_srcs]
+    std::vector<uint8_t>& blk = h->h_aux;
+    blk.resize(kLutBytes + sizeof(RecFrame) * (size_t)n_srcs);
+    block_lut(h, cfg, blk.data());
+    for (int s = 0; s < n_srcs; s++) {
+        RoiRec r;
+        memset(&r, 0, sizeof(r));
+        for (int p = 0; p < 3; p++) { r.plane[p] = srcs[s].planes[p]; r.pitch[p] = srcs[s].pitch[p]; }
+        r.width = (uint16_t)srcs[s].width; r.height = (uint16_t)srcs[s].height;
+        memcpy(blk.data() + kLutBytes + sizeof(RecFrame) * (size_t)s, &r, sizeof(RecFrame));
+    }
+    if (int rc = grow_device(&h->dev_recs, &h->dev_recs_cap, sizeof(RoiRec) * (size_t)units, who)) return rc;
+    const uint8_t* d_blk = nullptr;
+    {
+        HipRings b;
+        if (int rc = h->ring.upload(b, h->stream, blk.data(), blk.size(), &d_blk)) return rc;
+    }
+    if (h->opt_timing) HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    DParams d{};
+    d.rois = list->rois;
+    d.count = list->count;
+    d.srcs = reinterpret_cast<const uint4*>(d_blk + kLutBytes);
+    d.recs = static_cast<RoiRec*>(h->dev_recs);
+    d.status = status;
+    d.cap = cap; d.n_srcs = n_srcs; d.tiles = base; d.TH = q.TH; d.DH = DH; d.fmt = f;
+    hipLaunchKernelGGL(evam_pp_roi_records, dim3((unsigned)((units + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, d);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    q.recs = d.recs;
+    q.lut = reinterpret_cast<const float*>(d_blk);
+    q.dst = dst->data;
+    q.mode = cfg->resize_mode;
+    q.placement = cfg->placement;
+    q.slot_offset = dst->slot_offset;
+    q.slot_stride = dst->slot_stride;
+    q.color_rgb = cfg->color_order == EVAM_COLOR_RGB;
+    q.fill = (uint32_t)cfg->fill[0] | ((uint32_t)cfg->fill[1] << 8) | ((uint32_t)cfg->fill[2] << 16);
+    q.prio = kn.prio;
+    e = launch_roi_dev(f, cfg->out_dtype, kn.roi_px, q, (int)units, lds, h->stream);
+    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    if (h->opt_timing) HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    h->timed = h->opt_timing != 0;
+    h->stats.n_items = cap;
+    h->stats.n_launches = 2;
+    h->stats.kernels = EVAM_KERNEL_ROI;
+    h->stats.src_bytes = 0;
+    h->stats.dst_bytes = (int64_t)cap * plane * 3 * esz;
+    return EVAM_PP_OK;
 }
 
 }  // extern "C"

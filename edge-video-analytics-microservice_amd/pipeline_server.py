@@ -380,8 +380,20 @@ class BatchHub:
         self._rings: dict = {}          # action stage hub key -> ClipRing shared by the device's action streams
         self._streams: list | None = None
         self.batches: list = []        # (key, units, requests) per executed batch (inspection / tests)
+        # Server option "device_rois": a gvadetect stage directly followed by gvaclassify runs as one launch-only
+        # batch under the device runner (launch_detect_classify); "device_rois_cap": entries of its device ROI list
+        # and rows of the classifier's tensor (default: max_batch).
+        self.device_rois = False
+        self.device_rois_cap = self.max_batch
+        self.fused_batches: list = []  # one dict per detect -> classify batch of that option: which path served it
+        self._seq = 0
         self._thread = threading.Thread(target=self._loop, name=f"evam-hub-{device}", daemon=True)
         self._thread.start()
+
+    def next_seq(self) -> int:
+        """A counter that orders the launches and completions recorded in ``fused_batches``."""
+        self._seq += 1
+        return self._seq
 
     def stream(self, slot: int = 0):
         """Slot's torch stream (None: one tick at a time, or no GPU: the thread's current stream)."""
@@ -715,10 +727,11 @@ class DeviceRunner:
                 # the application's frames were written on its own (default) stream
                 s.wait_stream(torch.cuda.default_stream(hub.device))
             depth = max(len(p.stages) for p, _ in work)
+            fused_next = set()  # (pipeline, stage index) of classify stages that ran in their detector's batch
             for k in range(depth):
                 groups: dict = {}
                 for p, items in work:
-                    if p in failed or k >= len(p.stages) or not items:
+                    if p in failed or k >= len(p.stages) or not items or (p, k) in fused_next:
                         continue
                     st = p.stages[k]
                     try:
@@ -730,7 +743,12 @@ class DeviceRunner:
                         fail(p, e)
                         continue
                     if units > 0:
-                        groups.setdefault(st.hub_key(), []).append((p, _Request(st, w, units, event=False)))
+                        key = st.hub_key()
+                        nxt = fusable_classify(p, k, items) if hub.device_rois else None
+                        if nxt is not None:
+                            key = ("detect+classify", key, nxt.hub_key())
+                            fused_next.add((p, k + 1))
+                        groups.setdefault(key, []).append((p, _Request(st, w, units, event=False)))
                 for key, reqs in groups.items():
                     i = 0
                     while i < len(reqs):  # chunks of at most max_batch units (at least one request)
@@ -741,10 +759,21 @@ class DeviceRunner:
                         chunk = reqs[i:j]
                         i = j
                         stage = chunk[0][1].stage
-                        defer = (hub.inflight > 1 and hasattr(stage, "launch_batch")
-                                 and all(k == len(p.stages) - 1 for p, _ in chunk))
+                        fused = key[0] == "detect+classify"
+                        last = k + 1 if fused else k  # the chain's stage this batch ends with
+                        defer = (hub.inflight > 1 and (fused or hasattr(stage, "launch_batch"))
+                                 and all(last == len(p.stages) - 1 for p, _ in chunk))
                         try:
-                            if defer:
+                            if fused:
+                                done = launch_detect_classify(hub, [(r, p.stages[k + 1]) for p, r in chunk],
+                                                              hub.pp(slot), hub.device_rois_cap)
+                                if done is None:
+                                    defer = False  # served by the host path, complete
+                                elif defer:
+                                    deferred.append((done, chunk))
+                                else:
+                                    done()
+                            elif defer:
                                 deferred.append((stage.launch_batch([r for _, r in chunk], hub.pp(slot)), chunk))
                             else:
                                 stage.run_batch([r for _, r in chunk], hub.pp(slot))
@@ -914,23 +943,36 @@ class DetectStage(_InferenceStage):
         (the model output's copy to the host, the detections attached to the frames). The device runner calls it
         after the next tick's launch when it keeps several ticks in flight."""
         run = [it for r in reqs for it in r.items]
-        out = self._tensor(len(run))
-        xfs = pp.convert([img for _, img, _ in run], out, self.info, want_transform="lazy")
-        raw = self.model.fn(out)
+        out, xfs, raw = self.enqueue(run, pp)
 
         def complete():
-            r = raw.detach().float().cpu().numpy() if hasattr(raw, "detach") else raw
-            W, H = self.model.input_size
-            labels = None
-            for pp_ in self.model.postprocs():
-                labels = pp_.get("labels", labels)
-            for k, dets in enumerate(P.parse_ssd_batch(r, self.threshold)):
-                if dets:
-                    _, img, fr = run[k]
-                    fr.regions.extend(P.detections_to_regions(dets, xfs[k], img.width, img.height, W, H, labels,
-                                                              model=self.model.name))
+            self.attach(run, xfs, raw)
         complete.out = out  # the tensor the kernel writes stays alive until its batch completes
         return complete
+
+    def enqueue(self, run, pp):
+        """Pre-processing of the frames of ``run`` and the model call on it, enqueued: (input tensor, lazy transforms,
+        the model's output)."""
+        out = self._tensor(len(run))
+        xfs = pp.convert([img for _, img, _ in run], out, self.info, want_transform="lazy")
+        return out, xfs, self.model.fn(out)
+
+    def labels(self):
+        labels = None
+        for pp_ in self.model.postprocs():
+            labels = pp_.get("labels", labels)
+        return labels
+
+    def attach(self, run, xfs, raw):
+        """The model output to the host, the detections attached to the frames of ``run``."""
+        r = raw.detach().float().cpu().numpy() if hasattr(raw, "detach") else raw
+        W, H = self.model.input_size
+        labels = self.labels()
+        for k, dets in enumerate(P.parse_ssd_batch(r, self.threshold)):
+            if dets:
+                _, img, fr = run[k]
+                fr.regions.extend(P.detections_to_regions(dets, xfs[k], img.width, img.height, W, H, labels,
+                                                          model=self.model.name))
 
     def run_batch(self, reqs, pp):
         """One launch over the frames of every request, completed before returning."""
@@ -1001,8 +1043,14 @@ class ClassifyStage(_InferenceStage):
 
     def run_batch(self, reqs, pp):
         """One ROI launch over the regions of every request (hub thread)."""
-        import numpy as np
+        frames, rois, owners = self.gather(reqs)
+        if not rois:
+            return
+        self.classify_rois(frames, rois, owners, pp)
 
+    @staticmethod
+    def gather(reqs):
+        """(frames, [(frame index, x, y, w, h)], [region]) of the prepared work of ``reqs``, in launch order."""
         frames, rois, owners = [], [], []
         for req in reqs:
             for _, img, todo in req.items:
@@ -1011,24 +1059,151 @@ class ClassifyStage(_InferenceStage):
                 for r in todo:
                     rois.append((idx, r.x, r.y, r.w, r.h))
                     owners.append(r)
-        if not rois:
-            return
+        return frames, rois, owners
+
+    def classify_rois(self, frames, rois, owners, pp):
+        """One ROI launch over host rects ``rois`` [(frame index, x, y, w, h)], the model call, and its results
+        attached to ``owners`` (the region of each rect)."""
+        import numpy as np
+
         from .preproc import RoiBatch
 
         out = self._tensor(len(rois))
         pp.convert(frames, out, self.info, rois=RoiBatch(np.asarray(rois, dtype=np.int32)))
-        res = self.model.fn(out)
+        self.attach_results(self.model.fn(out), owners)
+
+    def attach_results(self, res, owners):
+        """Rows [0, len(owners)) of the model's output(s) ``res`` to the host, converted and attached to ``owners``."""
         posts = self.model.postprocs() or [{}]
         if not isinstance(res, dict):
             res = {posts[0].get("layer_name", "classification"): res}
+        n = len(owners)
         for pp_ in posts:
             layer = pp_.get("layer_name") or next(iter(res))
             logits = res[layer]
+            if len(logits) != n:
+                logits = logits[:n]  # a device-list batch: the rows from the list's count on are unspecified
             logits = logits.detach().float().cpu().numpy() if hasattr(logits, "detach") else logits
             name = pp_.get("attribute_name", layer)
             tens = P.classify(logits, pp_.get("labels"), pp_.get("method", "max"), name, model=self.model.name)
             for r, t in zip(owners, tens):
                 r.tensors.append(t)
+
+
+def device_label_ids(labels, object_class):
+    """The detector label ids whose regions a classify stage with ``object-class`` set ``object_class`` crops
+    (None: every label). A region's label is ``labels[id]``, or ``str(id)`` for an id outside ``labels``."""
+    if object_class is None:
+        return None
+    ids = [i for i, name in enumerate(labels or ()) if name in object_class]
+    for s in object_class:
+        try:
+            v = int(s)
+        except ValueError:
+            continue
+        if str(v) == s and not (labels and 0 <= v < len(labels)):
+            ids.append(v)
+    return ids
+
+
+def fusable_classify(p, k, items):
+    """The gvaclassify stage that can run in one launch-only batch with the gvadetect stage ``p.stages[k]`` (server
+    option ``device_rois``), or None: it follows directly, classifies every frame and every region (intervals 1), takes
+    planar input, and the frames arrive without regions, so the regions it would select are exactly the detections
+    the device list holds."""
+    st = p.stages[k]
+    if not isinstance(st, DetectStage) or k + 1 >= len(p.stages):
+        return None
+    nxt = p.stages[k + 1]
+    if not isinstance(nxt, ClassifyStage) or nxt.interval != 1 or nxt.reclassify != 1 or nxt.model.layout != "nchw" \
+            or nxt.device != st.device:
+        return None
+    if any(fr._regions for _, _, fr in items):
+        return None
+    return nxt
+
+
+def launch_detect_classify(hub, pairs, pp, cap: int):
+    """One launch-only detect -> classify batch. ``pairs``: [(the detect request of a pipeline, its classify stage)].
+
+    Enqueued, in order: the detector's pre-processing, the detector, ``detections_to_rois`` into a device list of
+    ``cap`` entries, the device-list ``convert`` into a ``cap``-row tensor, the classifier on that tensor. Returns the
+    completion: it copies the detector output, the list's count and the logits, builds the regions with the host's own
+    functions and attaches classifier row j to the j-th region the classify stages select (the device list holds them
+    in that order; the count is checked against the host's number). Rows from the count on are dropped; regions
+    beyond ``cap`` are classified through the host path, so nothing is lost.
+
+    When the detector's output is not a device ``[n,K,7]`` / ``[n,1,K,7]`` tensor, or the frames are of several
+    formats, the batch runs today's path here and None is returned. ``hub.fused_batches`` records which path served
+    the batch."""
+    import numpy as np
+
+    from .preproc import DeviceRoiList, ImageBatch
+
+    det, cls = pairs[0][0].stage, pairs[0][1]
+    run = [it for r, _ in pairs for it in r.items]
+    entry = {"frames": len(run), "cap": cap, "fused": False, "reason": None, "count": None,
+             "launched": hub.next_seq(), "completed": None}
+    hub.fused_batches.append(entry)
+    if len(hub.fused_batches) > 4096:
+        del hub.fused_batches[:2048]
+    out, xfs, raw = det.enqueue(run, pp)
+
+    def prepared():
+        reqs = []
+        for r, c in pairs:
+            w, units = c.prepare(r.items)
+            if units > 0:
+                reqs.append(_Request(c, w, units, event=False))
+        return reqs
+
+    if not (getattr(raw, "is_cuda", False) and raw.shape[-1] == 7 and raw.shape[0] == len(run)
+            and (raw.dim() == 3 or (raw.dim() == 4 and raw.shape[1] == 1))):
+        entry["reason"] = "the detector's output is not a device [n,K,7] tensor"
+    elif len({img.fourcc for _, img, _ in run}) != 1:
+        entry["reason"] = "frames of several formats"
+    if entry["reason"]:
+        det.attach(run, xfs, raw)
+        reqs = prepared()
+        if reqs:
+            cls.run_batch(reqs, pp)
+        for q in reqs:
+            q.stage.finish(q.items)
+        entry["completed"] = hub.next_seq()
+        return None
+
+    import torch
+
+    d = raw.detach()
+    if d.dtype != torch.float32 or not d.is_contiguous():
+        d = d.float().contiguous()
+    batch = ImageBatch([img for _, img, _ in run])
+    lst = DeviceRoiList(cap, device=d.device)
+    pp.detections_to_rois(d, batch, xfs, det.model.input_size, det.threshold,
+                          device_label_ids(det.labels(), cls.object_class), lst)
+    ctens = cls._tensor(cap)
+    pp.convert(batch, ctens, cls.info, rois=lst)
+    res = cls.model.fn(ctens)
+    entry["fused"] = True
+
+    def complete():
+        det.attach(run, xfs, raw)
+        count = int(lst.count.cpu().numpy().view(np.uint32)[0])
+        reqs = prepared()
+        frames, rois, owners = ClassifyStage.gather(reqs)
+        if len(owners) != count:
+            raise RuntimeError(f"detect -> classify: the device list holds {count} regions, the host selects {len(owners)}")
+        m = min(count, cap)
+        if m:
+            cls.attach_results(res, owners[:m])
+        if count > cap:
+            cls.classify_rois(frames, rois[cap:], owners[cap:], pp)
+        for q in reqs:
+            q.stage.finish(q.items)
+        entry["count"] = count
+        entry["completed"] = hub.next_seq()
+    complete.out = (out, ctens, lst, d)  # what the kernels read and write stays alive until the batch completes
+    return complete
 
 
 _SECOND = operator.itemgetter(1)  # the Image of a (frame_index, Image, FrameResult) work item
@@ -1675,6 +1850,8 @@ class _Server:
                                                 target=o.get("batch_target"),
                                                 drain_timeout_s=float(o.get("drain_timeout_ms", 2000.0)) / 1e3,
                                                 inflight=int(o.get("inflight", 3)))
+                h.device_rois = bool(o.get("device_rois", False))
+                h.device_rois_cap = max(1, int(o.get("device_rois_cap") or h.max_batch))
             return h
 
     def runner(self, slot: int = 0) -> DeviceRunner:

@@ -151,6 +151,44 @@ class RoiBatch:
         return int(self.array.shape[0])
 
 
+class DeviceRoiList:
+    """A ROI list resident in device memory (``evam_roi_list``): ``rois`` int32 ``[cap, 5]`` rows of
+    (src_index, x, y, w, h) and ``count`` int32 ``[1]`` (the number of entries its producer accepted, which may exceed
+    ``cap``; the bits of a uint32). :meth:`HipPreProcessor.detections_to_rois` fills it,
+    ``HipPreProcessor.convert(..., rois=<DeviceRoiList>)`` crops its entries; the host reads neither."""
+
+    def __init__(self, cap: int, device="cuda"):
+        import torch
+
+        if int(cap) <= 0:
+            raise PreProcError(N.ERR_INVALID_ARG, f"DeviceRoiList: cap must be > 0, got {cap}")
+        self.cap = int(cap)
+        self.rois = torch.zeros((self.cap, 5), dtype=torch.int32, device=device)
+        self.count = torch.zeros((1,), dtype=torch.int32, device=device)
+        self._c = N.EvamRoiList(self.rois.data_ptr(), self.count.data_ptr(), self.cap, 0)
+        self.c_ref = ctypes.byref(self._c)
+
+    @property
+    def device(self):
+        return self.rois.device
+
+    def set(self, rois):
+        """Fill the list from host rects (an ``int32 [n, 5]`` array or what :class:`RoiBatch` takes), n <= cap: for
+        tests and for callers whose rects come from the host. Asynchronous on the current torch stream."""
+        import torch
+
+        a = RoiBatch(rois).array
+        if len(a) > self.cap:
+            raise PreProcError(N.ERR_INVALID_ARG, f"DeviceRoiList.set: {len(a)} rects for cap {self.cap}")
+        if len(a):
+            self.rois[:len(a)].copy_(torch.from_numpy(a))
+        self.count.fill_(len(a))
+        return self
+
+    def __len__(self):
+        return self.cap
+
+
 @dataclass
 class PreProcInfo:
     """Model input pre-processing description (DLS ``InputImageLayerDesc`` from a model-proc)."""
@@ -445,12 +483,15 @@ class HipPreProcessor:
 
     # -- the hot path ------------------------------------------------------------------------------
     def convert(self, srcs, out, info: PreProcInfo | None = None, rois: Iterable | None = None,
-                slot_offset: int = 0, slot_stride: int = 1, want_transform: bool = False, slots=None):
+                slot_offset: int = 0, slot_stride: int = 1, want_transform: bool = False, slots=None, status=None):
         """Pre-process ``srcs`` (or ``rois`` of them) into ``out`` ([N,3,H,W] uint8/float32, device; float16/bfloat16 with
         ``info.precision`` ``"FP16"`` / ``"BF16"``, see :func:`output_dtype`).
 
         ``srcs``: an :class:`ImageBatch` (marshalled once) or a sequence of :class:`Image`.
-        ``rois``: a :class:`RoiBatch`, an ``int32 [n, 5]`` array or a sequence of :class:`Roi`.
+        ``rois``: a :class:`RoiBatch`, an ``int32 [n, 5]`` array or a sequence of :class:`Roi`; or a
+        :class:`DeviceRoiList`: entry i below its count goes to slot ``slot_offset + i * slot_stride``, the slots from
+        the count on are not touched, nothing is returned, and ``status`` (None or an int32 ``[cap]`` device tensor)
+        receives 0 or the error of every entry (``evam_pp_run_device_rois``).
         Item i goes to slot ``slot_offset + i * slot_stride`` of ``out``, or to ``slots[i]`` when ``slots`` (one
         distinct slot per item, ``evam_pp_run_slots``) is given.
         Returns a list of :class:`Transform` when ``want_transform`` (``"lazy"``: a :class:`Transforms`
@@ -479,6 +520,26 @@ class HipPreProcessor:
             # holding one takes the keyed path every call
             d = info.__dict__
             self._last_cfg = None if any(v.__class__ is list for v in d.values()) else (info, dt, dict(d), cached)
+        if rois.__class__ is DeviceRoiList:
+            # the rects stay on the device (evam_pp_run_device_rois): no transforms, no explicit slots
+            if slots is not None or want_transform:
+                raise PreProcError(N.ERR_INVALID_ARG, "convert: a DeviceRoiList takes neither slots nor want_transform")
+            if status is not None:
+                torch = self._torch
+                if status.dtype != torch.int32 or status.dim() != 1 or status.shape[0] < rois.cap \
+                        or not status.is_contiguous():
+                    raise PreProcError(N.ERR_INVALID_ARG, f"convert: status must be a contiguous int32 [>= {rois.cap}] "
+                                                          f"tensor, got {status.dtype} {tuple(status.shape)}")
+                self._check_device(status)
+            self._check_device(rois.rois)
+            self._bind_stream()
+            rc = self._lib.evam_pp_run_device_rois(self._h, batch.c_array, len(batch), rois.c_ref, cached, tref,
+                                                   None if status is None else ctypes.c_void_p(status.data_ptr()))
+            if rc:
+                N.check(self._lib, rc)
+            return None
+        if status is not None:
+            raise PreProcError(N.ERR_INVALID_ARG, "convert: status belongs to a DeviceRoiList call")
         if rois is not None:
             rb = rois if isinstance(rois, RoiBatch) else RoiBatch(rois)
             n_items = len(rb)
@@ -505,6 +566,42 @@ class HipPreProcessor:
         if not want_transform:
             return None
         return Transforms(xf) if want_transform == "lazy" else list(Transforms(xf))
+
+    def detections_to_rois(self, det, frames, transforms, tensor_size, threshold: float, labels=None,
+                           out_list: DeviceRoiList | None = None):
+        """The rects a gvaclassify stage crops from a detector's SSD output, written into a device list with no host
+        round trip (``evam_pp_ssd_rois``): what ``postproc.parse_ssd_batch`` -> ``detections_to_regions`` ->
+        the label filter -> ``pipeline_server.roi_inside`` give on the host, in their order.
+
+        ``det``: a float32 device tensor ``[n, K, 7]`` or ``[n, 1, K, 7]``; ``frames``: the n frames (an
+        :class:`ImageBatch` or Images; only sizes are read); ``transforms``: what ``convert(..., want_transform=...)``
+        returned for the detector's input, or None (plain full-frame resizes); ``tensor_size``: ``(W, H)`` of that
+        input; ``labels``: accepted label ids, or None for all; ``out_list``: the list to fill (default: a new one of
+        n * K entries). Returns the list. Asynchronous, as :meth:`convert`."""
+        import numpy as np
+
+        torch = self._torch
+        batch = frames if isinstance(frames, ImageBatch) else ImageBatch(frames)
+        n = len(batch)
+        if det.dtype != torch.float32 or not det.is_contiguous() or det.dim() not in (3, 4) or det.shape[-1] != 7 \
+                or det.shape[0] != n or (det.dim() == 4 and det.shape[1] != 1):
+            raise PreProcError(N.ERR_INVALID_ARG, f"detections_to_rois: det must be a contiguous float32 [{n}, K, 7] or "
+                                                  f"[{n}, 1, K, 7] tensor, got {det.dtype} {tuple(det.shape)}")
+        self._check_device(det)
+        k = int(det.shape[-2])
+        if out_list is None:
+            out_list = DeviceRoiList(n * k, device=det.device)
+        self._check_device(out_list.rois)
+        xf = N.transforms_array(transforms, n)
+        lab = None if labels is None else np.ascontiguousarray(list(labels), dtype=np.int32)
+        self._bind_stream()
+        rc = self._lib.evam_pp_ssd_rois(
+            self._h, ctypes.c_void_p(det.data_ptr()), n, k, batch.c_array, xf, int(tensor_size[0]), int(tensor_size[1]),
+            float(threshold), None if lab is None else lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            0 if lab is None else int(lab.size), out_list.c_ref)
+        if rc:
+            N.check(self._lib, rc)
+        return out_list
 
     def export_bgr(self, srcs, out=None, color_space: str = "BGR"):
         """The packed ``[N,H,W,3]`` uint8 image of every frame of ``srcs`` at source size, in one launch: the frame

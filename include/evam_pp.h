@@ -246,6 +246,61 @@ size_t evam_pp_jpeg_bound(int width, int height);
 int evam_pp_encode_jpeg(evam_pp* h, const evam_image* srcs, int n_srcs, int quality,
                         void* dst, size_t dst_stride, uint32_t* sizes);
 
+/* ---- Device-resident detections (gvadetect -> gvaclassify with no host round trip). Added without a struct change,
+ * so the ABI version stays 3; a library built before them lacks the symbols.
+ *
+ * The host path of a detect -> classify chain copies the detector's [N,K,7] output back, parses it, maps the boxes
+ * through the item transforms, filters them and hands evam_pp_run an evam_roi array. The calls below keep those rects
+ * on the device: evam_pp_ssd_rois writes them into a device list, evam_pp_run_device_rois crops them from it. */
+
+/* A list of ROIs in DEVICE memory: rois has room for cap entries; *count is the number of entries the producer
+ * accepted, which may exceed cap (then only the first cap are stored). Both pointers are the caller's. */
+typedef struct evam_roi_list {
+    evam_roi* rois;
+    uint32_t* count;
+    int32_t cap;
+    int32_t reserved;
+} evam_roi_list;
+
+/* SSD DetectionOutput rows -> the rects a gvaclassify stage crops. det: device float[n_items][k][7], rows of
+ * (image_id, label, conf, x0, y0, x1, y1), box normalised to the tensor_w x tensor_h model input. Item i belongs to
+ * srcs[i] (HOST array; only width and height are read) and to xf[i] (HOST array of the transforms evam_pp_run returned
+ * for the detector's input, or NULL when every item was a plain full-frame resize). Per item, only the rows before
+ * the first image_id < 0 count. A row is accepted when conf >= threshold (compared as floats), its label truncated to
+ * an integer is one of labels[0, n_labels) (HOST array; NULL: every label), and the rect
+ *   x = floor(x0' * W + 0.5), w = floor((x1' - x0') * W + 0.5)   (y, h alike; x0', x1' the box mapped to the frame
+ *   through the transform and clipped to [0, 1], all in double)
+ * has w > 0, h > 0 and a non-empty intersection with the frame. A row with a non-finite box value is rejected.
+ * Accepted rects are written as evam_roi {src_index = i, x, y, w, h} in item order, then row order (an ordered
+ * compaction: the order of the host path); *list->count receives their total, list->rois the first list->cap.
+ * n_items and k: 1 .. 65535 each is served (EVAM_PP_ERR_INVALID_ARG beyond, for a NULL pointer, cap <= 0,
+ * n_labels < 0 or a tensor size <= 0). Asynchronous on the handle's stream; the host reads no device memory. */
+int evam_pp_ssd_rois(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs,
+                     const evam_transform* xf, int tensor_w, int tensor_h, float threshold,
+                     const int32_t* labels, int n_labels, const evam_roi_list* list);
+
+/* evam_pp_ssd_rois on HOST arrays (det, list->rois and list->count are host memory): the same shared arithmetic,
+ * for tests and for callers that already hold the detections on the host. Host-only helper. */
+int evam_pp_ssd_rois_host(const float* det, int n_items, int k, const evam_image* srcs,
+                          const evam_transform* xf, int tensor_w, int tensor_h, float threshold,
+                          const int32_t* labels, int n_labels, const evam_roi_list* list);
+
+/* evam_pp_run with the items taken from a device list: entry i, for i < min(*list->count, list->cap), is cropped
+ * from srcs[entry.src_index] and written to slot dst->slot_offset + i * dst->slot_stride. Slots from the count on are
+ * not touched. dst must hold the slot of entry cap - 1.
+ * status: NULL or a device int32[cap]. status[i] is 0, or EVAM_PP_ERR_EMPTY_ROI / EVAM_PP_ERR_INVALID_ARG for a rect
+ * that clips to nothing / a src_index outside [0, n_srcs); the slot of such an entry is not touched and every other
+ * entry is processed as usual. Entries from the count on have status 0.
+ * The host never reads the list and the call does not synchronise; it uploads a per-source table (planes, pitches,
+ * size) only. The launch covers cap entries in list order: a workgroup whose entry is past the count or invalid
+ * returns at once, so size cap for the detections expected, not for the worst case.
+ * Refused, with nothing launched: sources of more than one fourcc, EVAM_LAYOUT_NHWC, an output size the ROI kernel
+ * does not plan (EVAM_PP_ERR_UNSUPPORTED each); cap <= 0 or a NULL list / rois / count pointer
+ * (EVAM_PP_ERR_INVALID_ARG). Sources, cfg and dst are validated as evam_pp_run validates them.
+ * evam_pp_stats.kernels reports EVAM_KERNEL_ROI; n_items is cap; src_bytes is 0 (the rects are unknown to the host). */
+int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi_list* list,
+                            const evam_preproc* cfg, const evam_tensor* dst, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
