@@ -3438,303 +3438,214 @@ constexpr StagedShape kStagedShapes[] = {{2, 2}, {1, 2}};
 // Valid (column segments, rows per group): four waves split NSEGX x R evenly.
 constexpr bool staged_valid(int nsegx, int R) { return nsegx > 4 ? R == 1 : (nsegx == 4 ? true : R % (4 / nsegx) == 0); }
 
-template <int FMT, int OUT, int NSEGX, int R, int NBUF>
-hipError_t launch_staged_t(const SParams& p, int grid, int lds, hipStream_t s) {
-    if constexpr (staged_valid(NSEGX, R)) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)evam_pp_staged<FMT, OUT, R, NSEGX, NBUF>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((evam_pp_staged<FMT, OUT, R, NSEGX, NBUF>), dim3(grid), dim3(kThreads), lds, s, p);
-        return hipGetLastError();
-    } else {
-        return hipErrorInvalidValue;  // never selected: staged_plan() only returns compatible shapes
+constexpr bool staged_shape(int R, int nbuf) {
+    for (const StagedShape& ss : kStagedShapes)
+        if (ss.R == R && ss.nbuf == nbuf) return true;
+    return false;
+}
+
+// ---- kernel tables: runtime arguments -> template instantiation, one definition per family ----
+// A family lists the values each template parameter takes (fill), says which combinations are instantiated
+// (built) and where one sits in its table (index). expand_kernels() walks the product of the lists and calls the
+// family's put<...>() once per combination; the lookup reads the table through the same index(). Both the
+// occupancy query of a plan and the launch take the pointer from here, so a plan cannot be sized for one
+// instantiation and launched as another, and a new template parameter is one more list and one more digit in
+// one place. A combination that is not built looks up to nullptr: the call fails (launch_kernel), no neighbour
+// is launched in its place.
+template <int... V> struct Vals {};
+using Fmts = Vals<kNV12, kI420, kBGRX, kBGR>;
+using Outs = Vals<0, 1, 2>;  // out_kind()
+using Bools = Vals<0, 1>;
+using Pxs = Vals<1, 2, 4>;
+constexpr int px_digit(int px) { return px == 1 ? 0 : (px == 2 ? 1 : (px == 4 ? 2 : -1)); }
+
+template <int N>
+constexpr int table_size(const int (&dims)[N]) {
+    int n = 1;
+    for (int d : dims) n *= d;
+    return n;
+}
+// Mixed-radix position of the digits v (v[k] in [0, dims[k])), or -1 when one is out of range.
+template <int N>
+constexpr int table_index(const int (&dims)[N], const int (&v)[N]) {
+    int i = 0;
+    for (int k = 0; k < N; k++) {
+        if (v[k] < 0 || v[k] >= dims[k]) return -1;
+        i = i * dims[k] + v[k];
     }
+    return i;
 }
 
-template <int FMT, int OUT, int NSEGX>
-hipError_t launch_staged_s(int R, int nbuf, const SParams& p, int grid, int lds, hipStream_t s) {
-    (void)nbuf;
-    if (R == 2) return launch_staged_t<FMT, OUT, NSEGX, 2, 2>(p, grid, lds, s);
-    if (R == 1) return launch_staged_t<FMT, OUT, NSEGX, 1, 2>(p, grid, lds, s);
-    return hipErrorInvalidValue;
+template <class Fam, int... Done>
+void expand_kernels(const void** t) { Fam::template put<Done...>(t); }
+template <class Fam, int... Done, int... H, class... Rest>
+void expand_kernels(const void** t, Vals<H...>, Rest... rest) { (expand_kernels<Fam, Done..., H>(t, rest...), ...); }
+
+template <class Fam>
+const void* kernel_at(int index) {
+    struct Table {
+        const void* fn[table_size(Fam::kDims)] = {};
+        Table() { Fam::fill(fn); }
+    };
+    static const Table t;
+    return index < 0 ? nullptr : t.fn[index];
 }
 
-template <int FMT, int OUT>
-hipError_t launch_staged_n(int nsegx, int R, int nbuf, const SParams& p, int grid, int lds, hipStream_t s) {
-    switch (nsegx) {
-    case 4: return launch_staged_s<FMT, OUT, 4>(R, nbuf, p, grid, lds, s);
-    case 2: return launch_staged_s<FMT, OUT, 2>(R, nbuf, p, grid, lds, s);
-    default: return launch_staged_s<FMT, OUT, 1>(R, nbuf, p, grid, lds, s);
+struct GenericKernels {
+    static constexpr int kDims[] = {4, 3, 2};  // format, output kind, NHWC
+    static constexpr int index(int f, int o, int nhwc) { return table_index(kDims, {f, o, nhwc}); }
+    template <int F, int O, int N>
+    static void put(const void** t) { t[index(F, O, N)] = (const void*)evam_pp_kernel<F, O, N != 0>; }
+    static void fill(const void** t) { expand_kernels<GenericKernels>(t, Fmts{}, Outs{}, Bools{}); }
+};
+const void* generic_kernel(int f, int out_dtype, bool nhwc) {
+    const void* fn = kernel_at<GenericKernels>(GenericKernels::index(f, out_kind(out_dtype), nhwc));
+    if (!fn) fail(EVAM_PP_ERR_UNSUPPORTED, "no generic kernel for format %d, out_dtype %d, nhwc %d", f, out_dtype, (int)nhwc);
+    return fn;
+}
+
+struct RowsKernels {
+    static constexpr int kDims[] = {4, 2};  // format, output kind (u8 / fp32)
+    static constexpr int index(int f, int o) { return table_index(kDims, {f, o}); }
+    template <int F, int O>
+    static void put(const void** t) { t[index(F, O)] = (const void*)evam_pp_rows<F, O>; }
+    static void fill(const void** t) { expand_kernels<RowsKernels>(t, Fmts{}, Bools{}); }
+};
+const void* rows_kernel(int f, int out_dtype) {
+    const void* fn = kernel_at<RowsKernels>(RowsKernels::index(f, out_kind(out_dtype)));
+    if (!fn) fail(EVAM_PP_ERR_UNSUPPORTED, "no row kernel for format %d, out_dtype %d", f, out_dtype);
+    return fn;
+}
+
+struct StagedKernels {
+    static constexpr int kDims[] = {4, 2, 2, 3, 1};  // format, output kind (u8 / fp32), R 1 / 2, NSEGX 1 / 2 / 4, NBUF 2
+    static constexpr int index(int f, int o, int R, int nsegx, int nbuf) {
+        return table_index(kDims, {f, o, R - 1, px_digit(nsegx), nbuf - 2});
     }
-}
-
-hipError_t launch_staged(int f, int out, int nsegx, int R, int nbuf, const SParams& p, int grid, int lds,
-                         hipStream_t s) {
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_staged_n<kNV12, 0>(nsegx, R, nbuf, p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_staged_n<kNV12, 1>(nsegx, R, nbuf, p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_staged_n<kI420, 0>(nsegx, R, nbuf, p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_staged_n<kI420, 1>(nsegx, R, nbuf, p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_staged_n<kBGRX, 0>(nsegx, R, nbuf, p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_staged_n<kBGRX, 1>(nsegx, R, nbuf, p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_staged_n<kBGR, 0>(nsegx, R, nbuf, p, grid, lds, s);
-    default: return launch_staged_n<kBGR, 1>(nsegx, R, nbuf, p, grid, lds, s);
+    static constexpr bool built(int R, int nsegx, int nbuf) { return staged_shape(R, nbuf) && staged_valid(nsegx, R); }
+    template <int F, int O, int R, int NSEGX, int NBUF>
+    static void put(const void** t) {
+        if constexpr (built(R, NSEGX, NBUF)) t[index(F, O, R, NSEGX, NBUF)] = (const void*)evam_pp_staged<F, O, R, NSEGX, NBUF>;
     }
+    static void fill(const void** t) { expand_kernels<StagedKernels>(t, Fmts{}, Bools{}, Vals<1, 2>{}, Pxs{}, Vals<2>{}); }
+};
+const void* staged_kernel(int f, int out_dtype, int R, int nsegx, int nbuf) {
+    const void* fn = kernel_at<StagedKernels>(StagedKernels::index(f, out_kind(out_dtype), R, nsegx, nbuf));
+    if (!fn)
+        fail(EVAM_PP_ERR_UNSUPPORTED, "no staged kernel for format %d, out_dtype %d, R %d, nsegx %d, nbuf %d", f, out_dtype, R,
+             nsegx, nbuf);
+    return fn;
 }
 
-
-template <int FMT, int OUT>
-hipError_t launch_rows_t(const RParams& p, int grid, int lds, hipStream_t s) {
-    hipLaunchKernelGGL((evam_pp_rows<FMT, OUT>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_rows(int f, int out, const RParams& p, int grid, int lds, hipStream_t s) {
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_rows_t<kNV12, 0>(p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_rows_t<kNV12, 1>(p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_rows_t<kI420, 0>(p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_rows_t<kI420, 1>(p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_rows_t<kBGRX, 0>(p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_rows_t<kBGRX, 1>(p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_rows_t<kBGR, 0>(p, grid, lds, s);
-    default: return launch_rows_t<kBGR, 1>(p, grid, lds, s);
+// Interleaved (NHWC) output: PX = 4 only, u8 or fp32 (the planner takes nothing else), see evam_pp_wave.
+struct WaveKernels {
+    static constexpr int kDims[] = {4, 3, 3, 2, 2};  // format, output kind, PX 1 / 2 / 4, REUSE, NHWC
+    static constexpr int index(int f, int o, int px, int reuse, int nhwc) {
+        return table_index(kDims, {f, o, px_digit(px), reuse, nhwc});
     }
-}
-
-template <int FMT, int OUT>
-hipError_t launch_t(const KParams& p, int grid, int lds, hipStream_t s) {
-    hipLaunchKernelGGL((evam_pp_kernel<FMT, OUT>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
-}
-
-// Interleaved (NHWC) output: the same kernel with the interleaved store epilogue.
-template <int FMT, int OUT>
-hipError_t launch_nhwc_t(const KParams& p, int grid, int lds, hipStream_t s) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)evam_pp_kernel<FMT, OUT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
+    static constexpr bool built(int o, int px, int nhwc) { return !nhwc || (px == 4 && o < 2); }
+    template <int F, int O, int PX, int R, int N>
+    static void put(const void** t) {
+        if constexpr (built(O, PX, N)) t[index(F, O, PX, R, N)] = (const void*)evam_pp_wave<F, O, PX, R != 0, N != 0>;
     }
-    hipLaunchKernelGGL((evam_pp_kernel<FMT, OUT, true>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
+    static void fill(const void** t) { expand_kernels<WaveKernels>(t, Fmts{}, Outs{}, Pxs{}, Bools{}, Bools{}); }
+};
+const void* wave_kernel(int f, int out_dtype, int px, bool reuse, bool nhwc) {
+    const void* fn = kernel_at<WaveKernels>(WaveKernels::index(f, out_kind(out_dtype), px, reuse, nhwc));
+    if (!fn)
+        fail(EVAM_PP_ERR_UNSUPPORTED, "no wave kernel for format %d, out_dtype %d, px %d, reuse %d, nhwc %d", f, out_dtype, px,
+             (int)reuse, (int)nhwc);
+    return fn;
 }
 
-hipError_t launch(int f, int out, const KParams& p, int grid, int lds, hipStream_t s) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f) {
-        case kNV12: return launch_t<kNV12, 2>(p, grid, lds, s);
-        case kI420: return launch_t<kI420, 2>(p, grid, lds, s);
-        case kBGRX: return launch_t<kBGRX, 2>(p, grid, lds, s);
-        default: return launch_t<kBGR, 2>(p, grid, lds, s);
-        }
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_t<kNV12, 0>(p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_t<kNV12, 1>(p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_t<kI420, 0>(p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_t<kI420, 1>(p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_t<kBGRX, 0>(p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_t<kBGRX, 1>(p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_t<kBGR, 0>(p, grid, lds, s);
-    default: return launch_t<kBGR, 1>(p, grid, lds, s);
+// Ring depth: D = 2 (D 1 / 3 / 4 measured slower on C2 and C5, rounds 2-3: profiles/r03f_bench_lines.txt, C2 D 3
+// +2.7 us; the other depths were retired in round 5).
+#ifndef EVAM_PP_STRIP_DEPTH
+#define EVAM_PP_STRIP_DEPTH 2  // A/B builds only (tools/build_variant.sh -DEVAM_PP_STRIP_DEPTH=3)
+#endif
+constexpr int kStripD = EVAM_PP_STRIP_DEPTH;
+// No BGR strip kernel; the interleaved (NHWC) instantiations are fp32 only.
+struct StripKernels {
+    static constexpr int kDims[] = {3, 3, 2, 2, 2};  // format (NV12 / I420 / BGRx), output kind, PX 1 / 2, paired taps, NHWC
+    static constexpr int index(int f, int o, int px, int pr, int nhwc) { return table_index(kDims, {f, o, px - 1, pr, nhwc}); }
+    static constexpr bool built(int o, int nhwc) { return !nhwc || o == 1; }
+    template <int F, int O, int PX, int PR, int N>
+    static void put(const void** t) {
+        if constexpr (built(O, N)) t[index(F, O, PX, PR, N)] = (const void*)evam_pp_strip<F, O, kStripD, PX, PR, N != 0>;
     }
+    static void fill(const void** t) {
+        expand_kernels<StripKernels>(t, Vals<kNV12, kI420, kBGRX>{}, Outs{}, Vals<1, 2>{}, Bools{}, Bools{});
+    }
+};
+const void* strip_kernel(int f, int out_dtype, int px, int pr, bool nhwc) {
+    const void* fn = kernel_at<StripKernels>(StripKernels::index(f, out_kind(out_dtype), px, pr, nhwc));
+    if (!fn)
+        fail(EVAM_PP_ERR_UNSUPPORTED, "no strip kernel for format %d, out_dtype %d, px %d, paired %d, nhwc %d", f, out_dtype, px,
+             pr, (int)nhwc);
+    return fn;
 }
 
-hipError_t launch_nhwc(int f, int out, const KParams& p, int grid, int lds, hipStream_t s) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f) {
-        case kNV12: return launch_nhwc_t<kNV12, 2>(p, grid, lds, s);
-        case kI420: return launch_nhwc_t<kI420, 2>(p, grid, lds, s);
-        case kBGRX: return launch_nhwc_t<kBGRX, 2>(p, grid, lds, s);
-        default: return launch_nhwc_t<kBGR, 2>(p, grid, lds, s);
-        }
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_nhwc_t<kNV12, 0>(p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_nhwc_t<kNV12, 1>(p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_nhwc_t<kI420, 0>(p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_nhwc_t<kI420, 1>(p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_nhwc_t<kBGRX, 0>(p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_nhwc_t<kBGRX, 1>(p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_nhwc_t<kBGR, 0>(p, grid, lds, s);
-    default: return launch_nhwc_t<kBGR, 1>(p, grid, lds, s);
+// NV12 / I420, u8 / fp32; six-column lanes (DD) with PX = 4 only; the interleaved (NHWC) instantiations are u8, PX = 4.
+struct BandKernels {
+    static constexpr int kDims[] = {2, 2, 3, 2, 2};  // format (NV12 / I420), output kind (u8 / fp32), PX 1 / 2 / 4, DD, NHWC
+    static constexpr int index(int f, int o, int px, int dd, int nhwc) {
+        return table_index(kDims, {f, o, px_digit(px), dd, nhwc});
     }
-}
-
-template <int FMT, int OUT, int PX, int NB>
-hipError_t launch_roi_px(const QParams& p, int grid, int lds, hipStream_t s) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)evam_pp_roi<FMT, OUT, PX, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
+    static constexpr bool built(int o, int px, int dd, int nhwc) { return (!dd || px == 4) && (!nhwc || (o == 0 && px == 4)); }
+    template <int F, int O, int PX, int DD, int N>
+    static void put(const void** t) {
+        if constexpr (built(O, PX, DD, N)) t[index(F, O, PX, DD, N)] = (const void*)evam_pp_band<F, O, PX, DD, N != 0>;
     }
-    hipLaunchKernelGGL((evam_pp_roi<FMT, OUT, PX, NB>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
+    static void fill(const void** t) { expand_kernels<BandKernels>(t, Vals<kNV12, kI420>{}, Bools{}, Pxs{}, Bools{}, Bools{}); }
+};
+const void* band_kernel(int f, int out_dtype, int px, bool dd, bool nhwc) {
+    const void* fn = kernel_at<BandKernels>(BandKernels::index(f, out_kind(out_dtype), px, dd, nhwc));
+    if (!fn)
+        fail(EVAM_PP_ERR_UNSUPPORTED, "no band kernel for format %d, out_dtype %d, px %d, dd %d, nhwc %d", f, out_dtype, px,
+             (int)dd, (int)nhwc);
+    return fn;
 }
 
 // PX = 2 adjacent pixels per lane by default (round 5; 1 for odd output widths): one dwordx2 store per channel and
 // one row setup per 2 pixels, C3 +3.7 % over PX = 1 on one box (profiles/r05p_c3_roi_px_rmax_ab.txt; PX = 4 equals
 // PX = 1 there, round 2 measured it 8 % slower: lanes 4 pixels apart spread their LDS tap reads over more dwords).
 // (Three staging buffers, EVAM_PP_ROI_NBUF=3, measured neutral or slower for two rounds: retired in round 5.)
-template <int FMT, int OUT>
-hipError_t launch_roi_t(int px, int nb, const QParams& p, int grid, int lds, hipStream_t s) {
-    (void)nb;
-    if (px == 4 && p.DW % 4 == 0) return launch_roi_px<FMT, OUT, 4, 2>(p, grid, lds, s);
-    if (px == 2 && p.DW % 2 == 0) return launch_roi_px<FMT, OUT, 2, 2>(p, grid, lds, s);
-    return launch_roi_px<FMT, OUT, 1, 2>(p, grid, lds, s);
+// The device-list siblings (DEV): PX = 2, or 1 for odd output widths (EVAM_PP_ROI_PX = 4 is not built for them).
+constexpr int roi_px(int px, int DW, bool dev) {
+    if (dev) return (px == 2 || px == 4) && DW % 2 == 0 ? 2 : 1;
+    return (px == 4 || px == 2) && DW % px == 0 ? px : 1;
+}
+struct RoiKernels {
+    static constexpr int kDims[] = {4, 3, 3, 2};  // format, output kind, PX 1 / 2 / 4, DEV (two staging buffers each)
+    static constexpr int index(int f, int o, int px, int dev) { return table_index(kDims, {f, o, px_digit(px), dev}); }
+    static constexpr bool built(int px, int dev) { return !dev || px != 4; }
+    template <int F, int O, int PX, int DEV>
+    static void put(const void** t) {
+        if constexpr (built(PX, DEV)) t[index(F, O, PX, DEV)] = (const void*)evam_pp_roi<F, O, PX, 2, DEV != 0>;
+    }
+    static void fill(const void** t) { expand_kernels<RoiKernels>(t, Fmts{}, Outs{}, Pxs{}, Bools{}); }
+};
+const void* roi_kernel(int f, int out_dtype, int px, bool dev) {
+    const void* fn = kernel_at<RoiKernels>(RoiKernels::index(f, out_kind(out_dtype), px, dev));
+    if (!fn) fail(EVAM_PP_ERR_UNSUPPORTED, "no ROI kernel for format %d, out_dtype %d, px %d, dev %d", f, out_dtype, px, (int)dev);
+    return fn;
 }
 
-// The device-list siblings (DEV = true): PX = 2, or 1 for odd output widths (EVAM_PP_ROI_PX = 4 is not built for them).
-template <int FMT, int OUT, int PX>
-hipError_t launch_roi_dev_px(const QParams& p, int grid, int lds, hipStream_t s) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)evam_pp_roi<FMT, OUT, PX, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
+// Every kernel above takes one parameter struct by value, so the argument array has a single entry, and the
+// host-stub address from its table is what the launch, hipFuncSetAttribute and the occupancy query all receive.
+// `big_lds`: the families whose LDS carve can pass 64 KB (generic, staged, ROI) raise the kernel's limit first.
+// fn == nullptr: the lookup found no instantiation and has recorded which.
+int launch_kernel(const void* fn, dim3 grid, dim3 block, int lds, hipStream_t stream, const void* params,
+                  bool big_lds = false) {
+    if (!fn) return EVAM_PP_ERR_UNSUPPORTED;
+    if (big_lds && lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL((evam_pp_roi<FMT, OUT, PX, 2, true>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
-}
-constexpr int roi_dev_px(int px, int DW) { return (px == 2 || px == 4) && DW % 2 == 0 ? 2 : 1; }
-template <int FMT>
-hipError_t launch_roi_dev_t(int out, int px, const QParams& p, int grid, int lds, hipStream_t s) {
-    const int k = out_kind(out), pxv = roi_dev_px(px, p.DW);
-    if (pxv == 2)
-        return k == 0 ? launch_roi_dev_px<FMT, 0, 2>(p, grid, lds, s)
-             : k == 1 ? launch_roi_dev_px<FMT, 1, 2>(p, grid, lds, s) : launch_roi_dev_px<FMT, 2, 2>(p, grid, lds, s);
-    return k == 0 ? launch_roi_dev_px<FMT, 0, 1>(p, grid, lds, s)
-         : k == 1 ? launch_roi_dev_px<FMT, 1, 1>(p, grid, lds, s) : launch_roi_dev_px<FMT, 2, 1>(p, grid, lds, s);
-}
-hipError_t launch_roi_dev(int f, int out, int px, const QParams& p, int grid, int lds, hipStream_t s) {
-    switch (f) {
-    case kNV12: return launch_roi_dev_t<kNV12>(out, px, p, grid, lds, s);
-    case kI420: return launch_roi_dev_t<kI420>(out, px, p, grid, lds, s);
-    case kBGRX: return launch_roi_dev_t<kBGRX>(out, px, p, grid, lds, s);
-    default: return launch_roi_dev_t<kBGR>(out, px, p, grid, lds, s);
-    }
-}
-template <int FMT>
-const void* roi_dev_fn_t(int k, int pxv) {
-    if (pxv == 2)
-        return k == 0 ? (const void*)evam_pp_roi<FMT, 0, 2, 2, true>
-             : k == 1 ? (const void*)evam_pp_roi<FMT, 1, 2, 2, true> : (const void*)evam_pp_roi<FMT, 2, 2, 2, true>;
-    return k == 0 ? (const void*)evam_pp_roi<FMT, 0, 1, 2, true>
-         : k == 1 ? (const void*)evam_pp_roi<FMT, 1, 1, 2, true> : (const void*)evam_pp_roi<FMT, 2, 1, 2, true>;
-}
-const void* roi_dev_fn(int f, int out, int pxv) {
-    const int k = out_kind(out);
-    switch (f) {
-    case kNV12: return roi_dev_fn_t<kNV12>(k, pxv);
-    case kI420: return roi_dev_fn_t<kI420>(k, pxv);
-    case kBGRX: return roi_dev_fn_t<kBGRX>(k, pxv);
-    default: return roi_dev_fn_t<kBGR>(k, pxv);
-    }
-}
-
-hipError_t launch_roi(int f, int out, int px, int nb, const QParams& p, int grid, int lds, hipStream_t s) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f) {
-        case kNV12: return launch_roi_t<kNV12, 2>(px, nb, p, grid, lds, s);
-        case kI420: return launch_roi_t<kI420, 2>(px, nb, p, grid, lds, s);
-        case kBGRX: return launch_roi_t<kBGRX, 2>(px, nb, p, grid, lds, s);
-        default: return launch_roi_t<kBGR, 2>(px, nb, p, grid, lds, s);
-        }
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_roi_t<kNV12, 0>(px, nb, p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_roi_t<kNV12, 1>(px, nb, p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_roi_t<kI420, 0>(px, nb, p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_roi_t<kI420, 1>(px, nb, p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_roi_t<kBGRX, 0>(px, nb, p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_roi_t<kBGRX, 1>(px, nb, p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_roi_t<kBGR, 0>(px, nb, p, grid, lds, s);
-    default: return launch_roi_t<kBGR, 1>(px, nb, p, grid, lds, s);
-    }
-}
-
-template <int FMT, int OUT, int PX>
-hipError_t launch_wave_r(bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
-    if (reuse) hipLaunchKernelGGL((evam_pp_wave<FMT, OUT, PX, true>), dim3(grid), dim3(kThreads), lds, s, p);
-    else hipLaunchKernelGGL((evam_pp_wave<FMT, OUT, PX, false>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
-}
-
-template <int FMT, int OUT>
-hipError_t launch_wave_p(int px, bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
-    switch (px) {
-    case 4: return launch_wave_r<FMT, OUT, 4>(reuse, p, grid, lds, s);
-    case 2: return launch_wave_r<FMT, OUT, 2>(reuse, p, grid, lds, s);
-    default: return launch_wave_r<FMT, OUT, 1>(reuse, p, grid, lds, s);
-    }
-}
-
-hipError_t launch_wave(int f, int out, int px, bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f) {
-        case kNV12: return launch_wave_p<kNV12, 2>(px, reuse, p, grid, lds, s);
-        case kI420: return launch_wave_p<kI420, 2>(px, reuse, p, grid, lds, s);
-        case kBGRX: return launch_wave_p<kBGRX, 2>(px, reuse, p, grid, lds, s);
-        default: return launch_wave_p<kBGR, 2>(px, reuse, p, grid, lds, s);
-        }
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_wave_p<kNV12, 0>(px, reuse, p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_wave_p<kNV12, 1>(px, reuse, p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_wave_p<kI420, 0>(px, reuse, p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_wave_p<kI420, 1>(px, reuse, p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_wave_p<kBGRX, 0>(px, reuse, p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_wave_p<kBGRX, 1>(px, reuse, p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_wave_p<kBGR, 0>(px, reuse, p, grid, lds, s);
-    default: return launch_wave_p<kBGR, 1>(px, reuse, p, grid, lds, s);
-    }
-}
-
-// Interleaved (NHWC) output: PX = 4 only (the planner takes nothing else), see evam_pp_wave.
-template <int FMT, int OUT>
-hipError_t launch_wave_nhwc_t(bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
-    if (reuse) hipLaunchKernelGGL((evam_pp_wave<FMT, OUT, 4, true, true>), dim3(grid), dim3(kThreads), lds, s, p);
-    else hipLaunchKernelGGL((evam_pp_wave<FMT, OUT, 4, false, true>), dim3(grid), dim3(kThreads), lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_wave_nhwc(int f, int out, bool reuse, const WParams& p, int grid, int lds, hipStream_t s) {
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_wave_nhwc_t<kNV12, 0>(reuse, p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_wave_nhwc_t<kNV12, 1>(reuse, p, grid, lds, s);
-    case kI420 * 2 + 0: return launch_wave_nhwc_t<kI420, 0>(reuse, p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_wave_nhwc_t<kI420, 1>(reuse, p, grid, lds, s);
-    case kBGRX * 2 + 0: return launch_wave_nhwc_t<kBGRX, 0>(reuse, p, grid, lds, s);
-    case kBGRX * 2 + 1: return launch_wave_nhwc_t<kBGRX, 1>(reuse, p, grid, lds, s);
-    case kBGR * 2 + 0: return launch_wave_nhwc_t<kBGR, 0>(reuse, p, grid, lds, s);
-    default: return launch_wave_nhwc_t<kBGR, 1>(reuse, p, grid, lds, s);
-    }
-}
-
-template <int FMT, int OUT>
-const void* wave_fn_t(int px, bool reuse) {
-    switch (px * 2 + (reuse ? 1 : 0)) {
-    case 9: return (const void*)evam_pp_wave<FMT, OUT, 4, true>;
-    case 8: return (const void*)evam_pp_wave<FMT, OUT, 4, false>;
-    case 5: return (const void*)evam_pp_wave<FMT, OUT, 2, true>;
-    case 4: return (const void*)evam_pp_wave<FMT, OUT, 2, false>;
-    case 3: return (const void*)evam_pp_wave<FMT, OUT, 1, true>;
-    default: return (const void*)evam_pp_wave<FMT, OUT, 1, false>;
-    }
-}
-const void* wave_fn(int f, int out, int px, bool reuse) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f) {
-        case kNV12: return wave_fn_t<kNV12, 2>(px, reuse);
-        case kI420: return wave_fn_t<kI420, 2>(px, reuse);
-        case kBGRX: return wave_fn_t<kBGRX, 2>(px, reuse);
-        default: return wave_fn_t<kBGR, 2>(px, reuse);
-        }
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return wave_fn_t<kNV12, 0>(px, reuse);
-    case kNV12 * 2 + 1: return wave_fn_t<kNV12, 1>(px, reuse);
-    case kI420 * 2 + 0: return wave_fn_t<kI420, 0>(px, reuse);
-    case kI420 * 2 + 1: return wave_fn_t<kI420, 1>(px, reuse);
-    case kBGRX * 2 + 0: return wave_fn_t<kBGRX, 0>(px, reuse);
-    case kBGRX * 2 + 1: return wave_fn_t<kBGRX, 1>(px, reuse);
-    case kBGR * 2 + 0: return wave_fn_t<kBGR, 0>(px, reuse);
-    default: return wave_fn_t<kBGR, 1>(px, reuse);
-    }
+    void* args[] = {const_cast<void*>(params)};
+    hipError_t e = hipLaunchKernel(fn, grid, block, args, (size_t)lds, stream);
+    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return EVAM_PP_OK;
 }
 
 // Workgroups of `fn` (256 threads, `lds` bytes of dynamic LDS) resident per CU: registers and LDS both
@@ -3746,11 +3657,24 @@ int resident_per_cu(const void* fn, int lds, int threads = kThreads) {
     auto it = cache.find({fn, lds, threads});
     if (it != cache.end()) return it->second;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, (size_t)lds) != hipSuccess || n <= 0)
+    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, (size_t)lds) != hipSuccess || n <= 0)
         n = std::max(1, std::min(8, (160 * 1024) / std::max(lds, 1)));
     cache[{fn, lds, threads}] = n;
     return n;
 }
+
+// What the launches of one uniform-geometry format group share. A plan_* function fills the kernel its plan was
+// sized for (from the family's table), the workgroup size, the dynamic LDS and the grid of a launch of n items:
+// (gx, gy, n) where gy > 0, else n * tiles_per_item workgroups. plan_uniform adds the family and the parameter
+// struct that plan filled.
+struct LaunchPlan {
+    uint32_t family = 0;     // the family's EVAM_KERNEL_* bit (0: no uniform-geometry kernel serves the group)
+    const void* fn = nullptr;
+    int block = kThreads, lds = 0;
+    int gx = 0, gy = 0, tiles_per_item = 0;
+    void* params = nullptr;  // TParams (strip, band), WParams, SParams or RParams
+    ItemArg* items = nullptr;  // its items[kArgItems]
+};
 
 // Wave-row kernel plan for a uniform-geometry group: pixels per lane PX (the widest whose staging
 // fits the LDS budget and divides DW), the exact per-tile footprint from the host tables, REUSE when
@@ -3760,12 +3684,13 @@ int resident_per_cu(const void* fn, int lds, int threads = kThreads) {
 // case over every residue x0 mod 32 present in the group (x0_mask bit r), which covers the 16-byte
 // phase of every plane (luma / packed at bpp 1, 3, 4; NV12 chroma 2 (x >> 1); I420 chroma x >> 1).
 bool plan_wave(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-               const YTab* yt, uint32_t x0_mask, const Knobs& kn, WParams& w, int& px, bool& reuse, int& lds,
-               int& grid, int only_px = 0) {
+               const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool nhwc, WParams& w, bool& reuse, LaunchPlan& k) {
     const int npc = f == kI420 ? 2 : (f == kNV12 ? 1 : 0);
     const int lut = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
     const int budget = kn.wave_lds;
-    const int want_px = only_px ? only_px : kn.px;  // only_px: the interleaved variant exists for PX = 4 alone
+    const int want_px = nhwc ? 4 : kn.px;  // the interleaved variant exists for PX = 4 alone
+    int px = 0, lds = 0;
+    w = WParams{};
     if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
     reuse = false;
     for (int Y = 0; Y + 1 < DH; Y++) {
@@ -3800,68 +3725,19 @@ bool plan_wave(int f, const Geom& g, int DW, int DH, int count, int out_dtype, i
     // longer per-wave row runs amortise the prologue better than more waves hide latency. C1: 16-row
     // tiles at the 5 workgroups per CU its registers allow ran 1.6 rounds, 31.9 us; 28-row tiles (one
     // round at 5 per CU) 31.6 us; 32-row tiles (one round at 4 per CU) 29.6 us (profiles/r02r_c1_sweep.txt).
-    const int per_cu = std::min(4, resident_per_cu(wave_fn(f, out_dtype, px, reuse), lds));
+    k.fn = wave_kernel(f, out_dtype, px, reuse, nhwc);
+    const int per_cu = std::min(4, resident_per_cu(k.fn, lds));
     const int64_t slots = (int64_t)n_cu * per_cu;
     int64_t rpw = ((int64_t)count * w.tiles_x * DH + 4 * slots - 1) / (4 * slots);
     rpw = std::max<int64_t>(2, std::min<int64_t>(32, rpw));
     w.TH = std::max(1, std::min(std::min(DH, 4 * 64), kn.wth > 0 ? kn.wth : (int)(4 * rpw)));  // <= 64 rows per wave
     w.tiles_per_item = w.tiles_x * ((DH + w.TH - 1) / w.TH);
-    const int64_t gr = (int64_t)count * w.tiles_per_item;
-    if (gr > 0x7FFFFFFF) return false;
-    grid = (int)gr;
+    if ((int64_t)count * w.tiles_per_item > 0x7FFFFFFF) return false;
+    k.block = kThreads;
+    k.lds = lds;
+    k.gy = 0;
+    k.tiles_per_item = w.tiles_per_item;
     return true;
-}
-
-// Ring depth: D = 2 (D 1 / 3 / 4 measured slower on C2 and C5, rounds 2-3: profiles/r03f_bench_lines.txt, C2 D 3
-// +2.7 us; the other depths were retired in round 5).
-#ifndef EVAM_PP_STRIP_DEPTH
-#define EVAM_PP_STRIP_DEPTH 2  // A/B builds only (tools/build_variant.sh -DEVAM_PP_STRIP_DEPTH=3)
-#endif
-constexpr int kStripD = EVAM_PP_STRIP_DEPTH;
-template <int FMT, int OUT, int PX>
-const void* strip_fn_p(int pr) {
-    return pr ? (const void*)evam_pp_strip<FMT, OUT, kStripD, PX, 1> : (const void*)evam_pp_strip<FMT, OUT, kStripD, PX, 0>;
-}
-const void* strip_fn(int f, int out, int pr, int px) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f * 2 + (px == 2)) {
-        case kNV12 * 2: return strip_fn_p<kNV12, 2, 1>(pr);
-        case kNV12 * 2 + 1: return strip_fn_p<kNV12, 2, 2>(pr);
-        case kI420 * 2: return strip_fn_p<kI420, 2, 1>(pr);
-        case kI420 * 2 + 1: return strip_fn_p<kI420, 2, 2>(pr);
-        case kBGRX * 2: return strip_fn_p<kBGRX, 2, 1>(pr);
-        default: return strip_fn_p<kBGRX, 2, 2>(pr);
-        }
-    switch ((f * 2 + out) * 2 + (px == 2)) {
-    case (kNV12 * 2 + 0) * 2: return strip_fn_p<kNV12, 0, 1>(pr);
-    case (kNV12 * 2 + 0) * 2 + 1: return strip_fn_p<kNV12, 0, 2>(pr);
-    case (kNV12 * 2 + 1) * 2: return strip_fn_p<kNV12, 1, 1>(pr);
-    case (kNV12 * 2 + 1) * 2 + 1: return strip_fn_p<kNV12, 1, 2>(pr);
-    case (kI420 * 2 + 0) * 2: return strip_fn_p<kI420, 0, 1>(pr);
-    case (kI420 * 2 + 0) * 2 + 1: return strip_fn_p<kI420, 0, 2>(pr);
-    case (kI420 * 2 + 1) * 2: return strip_fn_p<kI420, 1, 1>(pr);
-    case (kI420 * 2 + 1) * 2 + 1: return strip_fn_p<kI420, 1, 2>(pr);
-    case (kBGRX * 2 + 0) * 2: return strip_fn_p<kBGRX, 0, 1>(pr);
-    case (kBGRX * 2 + 0) * 2 + 1: return strip_fn_p<kBGRX, 0, 2>(pr);
-    case (kBGRX * 2 + 1) * 2: return strip_fn_p<kBGRX, 1, 1>(pr);
-    default: return strip_fn_p<kBGRX, 1, 2>(pr);
-    }
-}
-
-// The interleaved (NHWC, fp32) instantiations.
-template <int FMT, int PX>
-const void* strip_nhwc_fn_p(int pr) {
-    return pr ? (const void*)evam_pp_strip<FMT, 1, kStripD, PX, 1, true> : (const void*)evam_pp_strip<FMT, 1, kStripD, PX, 0, true>;
-}
-const void* strip_nhwc_fn(int f, int pr, int px) {
-    switch (f * 2 + (px == 2)) {
-    case kNV12 * 2: return strip_nhwc_fn_p<kNV12, 1>(pr);
-    case kNV12 * 2 + 1: return strip_nhwc_fn_p<kNV12, 2>(pr);
-    case kI420 * 2: return strip_nhwc_fn_p<kI420, 1>(pr);
-    case kI420 * 2 + 1: return strip_nhwc_fn_p<kI420, 2>(pr);
-    case kBGRX * 2: return strip_nhwc_fn_p<kBGRX, 1>(pr);
-    default: return strip_nhwc_fn_p<kBGRX, 2>(pr);
-    }
 }
 
 // Strip-kernel plan for a uniform 4:2:0 group (fills everything in TParams but the items, LUT, output
@@ -3882,8 +3758,7 @@ const void* strip_nhwc_fn(int f, int pr, int px) {
 // 1 KB per strip, or consecutive output rows that share source rows (vertical upscales: the wave kernel's
 // REUSE path).
 bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-                const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool pair_ok, TParams& p, int& pr, int& px, int& lds,
-                int& grid, bool nhwc = false) {
+                const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool pair_ok, bool nhwc, TParams& p, LaunchPlan& k) {
     if (f != kNV12 && f != kI420 && f != kBGRX) return false;
     int shared = 0, vis = 0;
     for (int Y = 0; Y + 1 < DH; Y++) {
@@ -3896,7 +3771,7 @@ bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, 
     if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
     const int npc = f == kI420 ? 2 : (f == kBGRX ? 0 : 1);
     int mY = 0, mC = 0;
-    px = 0;
+    int px = 0;
     for (int cand : {2, 1}) {
         if (kn.strip_px > 0 && cand != kn.strip_px) continue;
         // 128-column strips only where they still give a workgroup 4 strips per row: C5 (224 columns: two
@@ -3910,7 +3785,7 @@ bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, 
     if (!px) return false;
     const int nstrips = (DW + 64 * px - 1) / (64 * px);
     if (nstrips > kMaxStrips) return false;
-    pr = kn.strip_pair && pair_ok && mY <= 32 && (npc == 0 || (npc == 1 && mC <= 32) || (npc == 2 && mC <= 16)) ? 1 : 0;
+    const int pr = kn.strip_pair && pair_ok && mY <= 32 && (npc == 0 || (npc == 1 && mC <= 32) || (npc == 2 && mC <= 16)) ? 1 : 0;
     // one ring entry: 2 luma + 2 x npc chroma segments (paired: 1 KB per plane group)
     const int grp_bytes = pr ? (npc ? 2048 : 1024) : (2 + 2 * npc) * strip_slot(f, px);
     int nw = 4, best = 1 << 30;
@@ -3925,10 +3800,10 @@ bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, 
     const int lut_static = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 16;  // the kernel's static LDS
     const int wg_target = std::max(1, std::min(32, kn.strip_waves) / nw);
     p.wave_bytes = kStripD * grp_bytes;
-    lds = nw * p.wave_bytes + 16;  // dynamic LDS; + 16: a right-edge tap reads past its footprint (weight 0)
+    const int lds = nw * p.wave_bytes + 16;  // dynamic LDS; + 16: a right-edge tap reads past its footprint (weight 0)
     if (lds + lut_static > 64 * 1024) return false;
-    const void* const fn = nhwc ? strip_nhwc_fn(f, pr, px) : strip_fn(f, out_dtype, pr, px);
-    const int res = std::max(1, std::min(wg_target, resident_per_cu(fn, lds)));
+    k.fn = strip_kernel(f, out_dtype, px, pr, nhwc);
+    const int res = std::max(1, std::min(wg_target, resident_per_cu(k.fn, lds)));
     const int64_t slots = (int64_t)n_cu * res;
     const int64_t work = (int64_t)std::min(count, kArgItems) * p.tiles_x * DH;
     int th = (int)std::max<int64_t>(1, (work + slots - 1) / slots);
@@ -3947,64 +3822,17 @@ bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, 
         p.sfoot[k] = w < nw && s < nstrips && Xv0 <= Xv1 ? int2{xt[Xv0].s0, xt[Xv1].s1} : int2{-1, -1};
     }
     if ((p.tiles_x - 1) * 8 + nw > kSfoot) return false;
-    const int64_t gr = (int64_t)std::min(count, kArgItems) * p.tiles_per_item;
-    if (gr > 0x7FFFFFFF) return false;
-    grid = (int)gr;
+    if ((int64_t)std::min(count, kArgItems) * p.tiles_per_item > 0x7FFFFFFF) return false;
+    // grid (tile column, tile row, item), dispatched in that order (the C2 data movement in the strip pattern takes
+    // 1.7 us longer with each XCD on its own run of tiles, profiles/r03c_strip_bw.txt)
+    k.block = 64 * nw;
+    k.lds = lds;
+    k.gx = p.tiles_x;
+    k.gy = (DH + p.TH - 1) / p.TH;
+    k.tiles_per_item = p.tiles_per_item;
     return true;
 }
 
-template <int FMT, int OUT, int PX>
-hipError_t launch_strip_t(int pr, const TParams& p, dim3 grid, int lds, hipStream_t s) {
-    const dim3 blk(64 * p.nw);
-    if (pr) hipLaunchKernelGGL((evam_pp_strip<FMT, OUT, kStripD, PX, 1>), grid, blk, lds, s, p);
-    else hipLaunchKernelGGL((evam_pp_strip<FMT, OUT, kStripD, PX, 0>), grid, blk, lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_strip(int f, int out, int pr, int px, const TParams& p, dim3 grid, int lds, hipStream_t s) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f * 2 + (px == 2)) {
-        case kNV12 * 2: return launch_strip_t<kNV12, 2, 1>(pr, p, grid, lds, s);
-        case kNV12 * 2 + 1: return launch_strip_t<kNV12, 2, 2>(pr, p, grid, lds, s);
-        case kI420 * 2: return launch_strip_t<kI420, 2, 1>(pr, p, grid, lds, s);
-        case kI420 * 2 + 1: return launch_strip_t<kI420, 2, 2>(pr, p, grid, lds, s);
-        case kBGRX * 2: return launch_strip_t<kBGRX, 2, 1>(pr, p, grid, lds, s);
-        default: return launch_strip_t<kBGRX, 2, 2>(pr, p, grid, lds, s);
-        }
-    switch ((f * 2 + out) * 2 + (px == 2)) {
-    case (kNV12 * 2 + 0) * 2: return launch_strip_t<kNV12, 0, 1>(pr, p, grid, lds, s);
-    case (kNV12 * 2 + 0) * 2 + 1: return launch_strip_t<kNV12, 0, 2>(pr, p, grid, lds, s);
-    case (kNV12 * 2 + 1) * 2: return launch_strip_t<kNV12, 1, 1>(pr, p, grid, lds, s);
-    case (kNV12 * 2 + 1) * 2 + 1: return launch_strip_t<kNV12, 1, 2>(pr, p, grid, lds, s);
-    case (kI420 * 2 + 0) * 2: return launch_strip_t<kI420, 0, 1>(pr, p, grid, lds, s);
-    case (kI420 * 2 + 0) * 2 + 1: return launch_strip_t<kI420, 0, 2>(pr, p, grid, lds, s);
-    case (kI420 * 2 + 1) * 2: return launch_strip_t<kI420, 1, 1>(pr, p, grid, lds, s);
-    case (kI420 * 2 + 1) * 2 + 1: return launch_strip_t<kI420, 1, 2>(pr, p, grid, lds, s);
-    case (kBGRX * 2 + 0) * 2: return launch_strip_t<kBGRX, 0, 1>(pr, p, grid, lds, s);
-    case (kBGRX * 2 + 0) * 2 + 1: return launch_strip_t<kBGRX, 0, 2>(pr, p, grid, lds, s);
-    case (kBGRX * 2 + 1) * 2: return launch_strip_t<kBGRX, 1, 1>(pr, p, grid, lds, s);
-    default: return launch_strip_t<kBGRX, 1, 2>(pr, p, grid, lds, s);
-    }
-}
-
-template <int FMT, int PX>
-hipError_t launch_strip_nhwc_t(int pr, const TParams& p, dim3 grid, int lds, hipStream_t s) {
-    const dim3 blk(64 * p.nw);
-    if (pr) hipLaunchKernelGGL((evam_pp_strip<FMT, 1, kStripD, PX, 1, true>), grid, blk, lds, s, p);
-    else hipLaunchKernelGGL((evam_pp_strip<FMT, 1, kStripD, PX, 0, true>), grid, blk, lds, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_strip_nhwc(int f, int pr, int px, const TParams& p, dim3 grid, int lds, hipStream_t s) {
-    switch (f * 2 + (px == 2)) {
-    case kNV12 * 2: return launch_strip_nhwc_t<kNV12, 1>(pr, p, grid, lds, s);
-    case kNV12 * 2 + 1: return launch_strip_nhwc_t<kNV12, 2>(pr, p, grid, lds, s);
-    case kI420 * 2: return launch_strip_nhwc_t<kI420, 1>(pr, p, grid, lds, s);
-    case kI420 * 2 + 1: return launch_strip_nhwc_t<kI420, 2>(pr, p, grid, lds, s);
-    case kBGRX * 2: return launch_strip_nhwc_t<kBGRX, 1>(pr, p, grid, lds, s);
-    default: return launch_strip_nhwc_t<kBGRX, 2>(pr, p, grid, lds, s);
-    }
-}
 
 // Band-kernel plan for a uniform 4:2:0 group whose consecutive output rows share source rows (vertical
 // upscales, C1). Fills the geometry, strips, bands and LDS fields of TParams (not items, LUT, output,
@@ -4018,8 +3846,7 @@ hipError_t launch_strip_nhwc(int f, int pr, int px, const TParams& p, dim3 grid,
 // Returns false for geometries it does not suit (fewer than 1 in 8 rows sharing source rows, footprints
 // over 1 KB, outputs wider than kMaxStrips strips).
 bool plan_band(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-               const YTab* yt, uint32_t x0_mask, const Knobs& kn, TParams& p, int& px, bool& dd, int& nw, int& lds,
-               int only_px = 0) {
+               const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool nhwc, TParams& p, LaunchPlan& k) {
     if (f != kNV12 && f != kI420) return false;
     int shared = 0, vis = 0;
     for (int Y = 0; Y + 1 < DH; Y++) {
@@ -4032,10 +3859,10 @@ bool plan_band(int f, const Geom& g, int DW, int DH, int count, int out_dtype, i
     if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
     const int npc = f == kI420 ? 2 : 1;
     int mY = 0, mC = 0;
-    px = 0;
+    int px = 0, nw = 0, lds = 0;
     for (int cand : {4, 2, 1}) {
         if (kn.band_px > 0 && cand != kn.band_px) continue;
-        if (only_px && cand != only_px) continue;  // the interleaved variant exists for PX = 4 alone
+        if (nhwc && cand != 4) continue;  // the interleaved variant exists for PX = 4 alone
         if (DW % cand) continue;
         wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, 64 * cand, mY, mC);
         if (mY <= 64 && mC <= 64) { px = cand; break; }
@@ -4090,62 +3917,132 @@ bool plan_band(int f, const Geom& g, int DW, int DH, int count, int out_dtype, i
         const int Xv0 = std::max(s * sw, g.ox), Xv1 = std::min(std::min(s * sw + sw, DW), g.ox + g.rw) - 1;
         p.sfoot[k] = w < nw && s < nstrips && Xv0 <= Xv1 ? int2{xt[Xv0].s0, xt[Xv1].s1} : int2{-1, -1};
     }
-    dd = px == 4 && kn.band_dd && band_six_columns(xt, DW, x0_mask);
+    const bool dd = px == 4 && kn.band_dd && band_six_columns(xt, DW, x0_mask);
+    k.fn = band_kernel(f, out_dtype, px, dd, nhwc);
+    k.block = 64 * nw;
+    k.lds = lds;
+    k.gx = p.tiles_x;
+    k.gy = (DH + th - 1) / th;
+    k.tiles_per_item = p.tiles_per_item;
     return (int64_t)per_launch * p.tiles_per_item <= 0x7FFFFFFF;
 }
 
-template <int FMT, int OUT>
-hipError_t launch_band_t(int px, bool dd, const TParams& p, dim3 grid, int nw, int lds, hipStream_t s) {
-    const dim3 blk(64 * nw);
-    if (px == 4 && dd) hipLaunchKernelGGL((evam_pp_band<FMT, OUT, 4, 1>), grid, blk, lds, s, p);
-    else if (px == 4) hipLaunchKernelGGL((evam_pp_band<FMT, OUT, 4, 0>), grid, blk, lds, s, p);
-    else if (px == 2) hipLaunchKernelGGL((evam_pp_band<FMT, OUT, 2, 0>), grid, blk, lds, s, p);
-    else hipLaunchKernelGGL((evam_pp_band<FMT, OUT, 1, 0>), grid, blk, lds, s, p);
-    return hipGetLastError();
-}
-hipError_t launch_band(int f, int out, int px, bool dd, const TParams& p, dim3 grid, int nw, int lds, hipStream_t s) {
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return launch_band_t<kNV12, 0>(px, dd, p, grid, nw, lds, s);
-    case kNV12 * 2 + 1: return launch_band_t<kNV12, 1>(px, dd, p, grid, nw, lds, s);
-    case kI420 * 2 + 0: return launch_band_t<kI420, 0>(px, dd, p, grid, nw, lds, s);
-    default: return launch_band_t<kI420, 1>(px, dd, p, grid, nw, lds, s);
-    }
-}
-
-// The interleaved (NHWC, u8, PX = 4) instantiations.
-hipError_t launch_band_nhwc(int f, bool dd, const TParams& p, dim3 grid, int nw, int lds, hipStream_t s) {
-    const dim3 blk(64 * nw);
-    if (f == kNV12 && dd) hipLaunchKernelGGL((evam_pp_band<kNV12, 0, 4, 1, true>), grid, blk, lds, s, p);
-    else if (f == kNV12) hipLaunchKernelGGL((evam_pp_band<kNV12, 0, 4, 0, true>), grid, blk, lds, s, p);
-    else if (dd) hipLaunchKernelGGL((evam_pp_band<kI420, 0, 4, 1, true>), grid, blk, lds, s, p);
-    else hipLaunchKernelGGL((evam_pp_band<kI420, 0, 4, 0, true>), grid, blk, lds, s, p);
-    return hipGetLastError();
-}
-
-template <int FMT, int OUT>
-const void* roi_fn_t(int px, int nb) {
-    (void)nb;
-    return px == 4 ? (const void*)evam_pp_roi<FMT, OUT, 4, 2>
-         : px == 2 ? (const void*)evam_pp_roi<FMT, OUT, 2, 2> : (const void*)evam_pp_roi<FMT, OUT, 1, 2>;
-}
-const void* roi_fn(int f, int out, int px, int nb) {
-    if (out_kind(out) == 2)  // fp16 / bf16: the 2-byte instantiations
-        switch (f) {
-        case kNV12: return roi_fn_t<kNV12, 2>(px, nb);
-        case kI420: return roi_fn_t<kI420, 2>(px, nb);
-        case kBGRX: return roi_fn_t<kBGRX, 2>(px, nb);
-        default: return roi_fn_t<kBGR, 2>(px, nb);
+// Staged-kernel plan for a uniform group (u8 / fp32, planar): fills the geometry, tile and LDS fields of SParams.
+// Returns false where no tile width fits (the row kernel serves those) or EVAM_PP_STAGED=0.
+bool plan_staged(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
+                 const YTab* yt, uint32_t x0_mask, const Knobs& kn, SParams& sp, LaunchPlan& k) {
+    (void)yt;
+    // Tile width: the widest of 256 / 128 columns whose staged row segment (the exact widest footprint of
+    // any tile and crop origin of this group) fits the kernel's 1 KB slot.
+    auto seg_bytes = [&](int tw) {
+        int mY = 0, mC = 0;
+        wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, tw, mY, mC);
+        return 16 * std::max(1, std::max(mY, mC));
+    };
+    int nsegx = 0;
+    if (kn.staged)
+        for (int n : {4, 2}) {  // (64 columns would need R % 4 == 0: the row kernel serves those)
+            if (seg_bytes(64 * n) <= kSlot) { nsegx = n; break; }
         }
-    switch (f * 2 + out) {
-    case kNV12 * 2 + 0: return roi_fn_t<kNV12, 0>(px, nb);
-    case kNV12 * 2 + 1: return roi_fn_t<kNV12, 1>(px, nb);
-    case kI420 * 2 + 0: return roi_fn_t<kI420, 0>(px, nb);
-    case kI420 * 2 + 1: return roi_fn_t<kI420, 1>(px, nb);
-    case kBGRX * 2 + 0: return roi_fn_t<kBGRX, 0>(px, nb);
-    case kBGRX * 2 + 1: return roi_fn_t<kBGRX, 1>(px, nb);
-    case kBGR * 2 + 0: return roi_fn_t<kBGR, 0>(px, nb);
-    default: return roi_fn_t<kBGR, 1>(px, nb);
+    if (nsegx && kn.nsegx > 0 && kn.nsegx < nsegx && 2 % (4 / kn.nsegx) == 0) nsegx = kn.nsegx;
+    if (!nsegx) return false;
+    // Pipeline shape: R output rows per group, NBUF staging buffers (NBUF - 1 groups of DMA in
+    // flight).
+    int R = kn.stage_r > 0 ? kn.stage_r : 2, nbuf = 2;
+    if (!staged_shape(R, nbuf) || !staged_valid(nsegx, R)) { R = 2; nbuf = 2; }
+    sp = SParams{};
+    sp.DW = DW; sp.DH = DH;
+    const int tw = 64 * nsegx;
+    sp.tiles_x = (DW + tw - 1) / tw;
+    // ~4096 pixels per workgroup, but short enough tiles that small batches still put
+    // 8 workgroups on every CU (a whole clip-ring step is only 32 x 224 x 224 pixels).
+    // At most 16 rows: C4 (tw 128) runs 3-7 % faster at 16 than at 32 (profiles/r01ad_sweep_th*.txt).
+    int th = std::max(2, std::min(16, 4096 / tw));
+    const int64_t cols = (int64_t)std::min(count, kArgItems) * sp.tiles_x;
+    const int64_t want = 8 * (int64_t)n_cu;
+    if (cols * ((DH + th - 1) / th) < want) th = (int)std::max<int64_t>(2, cols * DH / want);
+    sp.TH = std::max(1, std::min(std::min(DH, 64), kn.th > 0 ? kn.th : th));  // <= 64: lane-held rows
+    sp.TH = std::min(64, (sp.TH + R - 1) / R * R);
+    sp.tiles_per_item = sp.tiles_x * ((DH + sp.TH - 1) / sp.TH);
+    const int np = f == kI420 ? 3 : (f == kNV12 ? 2 : 1);
+    sp.offBuf = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
+    sp.slot_bytes = seg_bytes(tw);  // <= the kernel's SLOT_MAX (tile choice above)
+    sp.buf_bytes = 2 * R * np * sp.slot_bytes;
+    sp.ntcol = sp.tiles_x <= kTCols ? sp.tiles_x : 0;
+    for (int c = 0; c < sp.ntcol; c++) {
+        const int Xv0 = std::max(c * tw, g.ox), Xv1 = std::min(std::min(c * tw + tw, DW), g.ox + g.rw) - 1;
+        sp.tcol[c] = Xv0 <= Xv1 ? int2{xt[Xv0].s0, xt[Xv1].s1} : int2{-1, -1};
     }
+    k.fn = staged_kernel(f, out_dtype, R, nsegx, nbuf);
+    k.block = kThreads;
+    k.lds = sp.offBuf + nbuf * sp.buf_bytes;
+    k.gy = 0;
+    k.tiles_per_item = sp.tiles_per_item;
+    return true;
+}
+
+// Row-kernel plan for a uniform group (u8 / fp32, planar): the tiles of choose_row_tiles. Serves every geometry.
+bool plan_rows(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
+               const YTab* yt, uint32_t x0_mask, const Knobs& kn, RParams& r, LaunchPlan& k) {
+    (void)g; (void)count; (void)n_cu; (void)xt; (void)yt; (void)x0_mask;
+    const RowCfg rc = choose_row_tiles(DW, DH, kn);
+    r = RParams{};
+    r.DW = DW; r.DH = DH;
+    r.TW = rc.TW; r.TH = rc.TH;
+    r.tiles_x = (DW + rc.TW - 1) / rc.TW;
+    r.tiles_per_item = r.tiles_x * ((DH + rc.TH - 1) / rc.TH);
+    r.nsegx = rc.TW / 64;
+    k.fn = rows_kernel(f, out_dtype);
+    k.block = kThreads;
+    k.lds = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
+    k.gy = 0;
+    k.tiles_per_item = r.tiles_per_item;
+    return true;
+}
+
+// The parameter structs of a uniform group's plan that are not kept on the handle (TParams is: 3.5 KB).
+struct UniformParams {
+    WParams w;
+    SParams s;
+    RParams r;
+};
+
+// The kernel choice for a uniform-geometry format group, in the one place that holds its order and guards:
+// strip, then band, then wave, then staged, then rows; the first family that is allowed (the EVAM_PP_STRIP / _BAND /
+// _WAVE / _STAGED knobs; 2 forces strip, band or wave past the others), instantiated for the output (layout,
+// element size) and whose plan takes the geometry serves the group. run_impl asks twice with the same arguments:
+// ahead of the descriptor block for interleaved and 16-bit groups (family 0: the generic kernel serves the group,
+// which needs its descriptors in the block), and at the launch for every uniform group.
+//  * strip: planar in every element type; interleaved in fp32 (12-byte stores, dword-aligned as the elements are).
+//  * band: u8 / fp32 planar; interleaved u8 with four-pixel stores where they are aligned (nhwc_wave_ok).
+//  * wave: where consecutive output rows share source rows (vertical upscale: REUSE), forced, or interleaved (four-
+//    pixel stores, nhwc_wave_ok); for downscales the staged kernel's deeper shared staging is faster.
+//  * staged, rows: planar u8 / fp32 only (not instantiated for 2-byte elements or interleaved stores).
+LaunchPlan plan_uniform(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
+                        const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool pair_ok, bool nhwc, bool nhwc_wave_ok,
+                        TParams& t, UniformParams& u) {
+    const bool half = out_kind(out_dtype) == 2;
+    LaunchPlan k;
+    bool reuse = false;
+    if (kn.strip && kn.wave != 2 && (!nhwc || out_dtype == EVAM_DTYPE_F32) &&
+        plan_strip(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, pair_ok, nhwc, t, k)) {
+        k.family = EVAM_KERNEL_STRIP; k.params = &t; k.items = t.items;
+    } else if (kn.band && kn.wave != 2 && kn.strip != 2 && !half && (!nhwc || (out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok)) &&
+               plan_band(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, nhwc, t, k)) {
+        k.family = EVAM_KERNEL_BAND; k.params = &t; k.items = t.items;
+    } else if (kn.wave && (!nhwc || nhwc_wave_ok) &&
+               plan_wave(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, nhwc, u.w, reuse, k) &&
+               (reuse || kn.wave == 2 || nhwc)) {
+        k.family = EVAM_KERNEL_WAVE; k.params = &u.w; k.items = u.w.items;
+    } else if (nhwc || half) {
+        k = LaunchPlan{};
+    } else if (plan_staged(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, u.s, k)) {
+        k.family = EVAM_KERNEL_STAGED; k.params = &u.s; k.items = u.s.items;
+    } else {
+        plan_rows(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, u.r, k);
+        k.family = EVAM_KERNEL_ROWS; k.params = &u.r; k.items = u.r.items;
+    }
+    return k;
 }
 
 // ROI-kernel plan for one format group with per-item geometry: the tile height, the LDS carve and the
@@ -4162,7 +4059,7 @@ const void* roi_fn(int f, int out, int px, int nb) {
 // 12 KB (EVAM_PP_ROI_BUF fixes it). `slots`: workgroups resident at once with that carve.
 constexpr int kRoiWavesPerSimd = 7;  // evam_pp_roi<*, *, 1> at kRoiK = 6: <= 72 VGPRs
 bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, int count, int n_cu, const Knobs& kn,
-              QParams& q, int& base_tiles, int& lds, int64_t& slots, bool dev = false) {
+              QParams& q, int& base_tiles, int& lds, int64_t& slots, const void*& fn, bool dev = false) {
     if (DW > kRoiK * kThreads || DH > 65535) return false;
     q.DW = DW; q.DH = DH;
     q.TH = (int64_t)DW * DH <= 32768 ? DH : std::max(8, std::min(DH, 16384 / DW));
@@ -4173,7 +4070,7 @@ bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, i
     q.offBuf = q.offYT + (int)sizeof(YTab) * q.TH;
     const int64_t grid = (int64_t)count * base_tiles;
     const int per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(kRoiWavesPerSimd, (grid + n_cu - 1) / n_cu));
-    const int pxv = dev ? roi_dev_px(px, DW) : ((px == 4 || px == 2) && DW % px == 0 ? px : 1);
+    const int pxv = roi_px(px, DW, dev);
     const uint32_t qw = (uint32_t)(DW / pxv);
     q.mqw = qw > 1 ? (uint32_t)((0x100000000ull + qw - 1) / qw) : 0u;
     const int nb = 2;
@@ -4182,7 +4079,7 @@ bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, i
     q.buf_bytes = (std::max(buf, max_row_bytes) + 15) & ~15;
     lds = q.offBuf + nb * q.buf_bytes;
     if (q.buf_bytes > 32 * 1024 || lds > 160 * 1024) return false;
-    const void* fn = dev ? roi_dev_fn(f, out_dtype, pxv) : roi_fn(f, out_dtype, pxv, nb);
+    fn = roi_kernel(f, out_dtype, pxv, dev);
     int res = resident_per_cu(fn, lds);
     while (kn.roi_buf <= 0 && res < per_cu && q.buf_bytes - 512 >= max_row_bytes) {
         q.buf_bytes -= 512;
@@ -4748,7 +4645,13 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     // band (u8) and wave kernels' four-pixel stores where they are aligned to their width: DW % 4 == 0 makes every row and slot
     // size a multiple of it, so the tensor's base decides (4 bytes for u8, 16 for fp32).
     const bool nhwc_wave_ok = DW % 4 == 0 && ((uintptr_t)dst->data & (uintptr_t)(esz == 4 ? 15 : 3)) == 0;
-    // Does a strip or wave plan serve interleaved uniform group f? Decided here, ahead of the descriptor block, so
+    // Uniform group f's plan (plan_uniform: the one kernel-choice cascade) on the host tables xt / yt.
+    UniformParams up;  // not cleared here: a plan_* function clears the struct it fills
+    auto plan_group = [&](int f, const XTab* xt, const YTab* yt, bool pair_ok) {
+        return plan_uniform(f, geo[rep[f]], DW, DH, count[f], cfg->out_dtype, h->n_cu, xt, yt, x0_mask[f], kn, pair_ok, nhwc,
+                            nhwc_wave_ok, h->sc_tparams, up);
+    };
+    // Does a uniform-geometry kernel serve interleaved uniform group f? Decided here, ahead of the descriptor block, so
     // that only a group the generic kernel serves puts its items' descriptors (which change with every set of
     // frames) into it; the launch below plans again with the same arguments. Memoised on those arguments.
     // The same question for a planar 16-bit group: the strip kernel, or the wave kernel where rows share source rows;
@@ -4768,26 +4671,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         h->sc_xt.resize((size_t)DW);
         h->sc_yt.resize((size_t)DH);
         build_tables(g, DW, DH, h->tab_cache, h->sc_xt.data(), h->sc_yt.data());
-        bool ok = false;
-        int px = 0, lds = 0, grid = 0;
-        if (kn.strip && kn.wave != 2 && (cfg->out_dtype == EVAM_DTYPE_F32 || !nhwc)) {
-            int pr = 0;
-            ok = plan_strip(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f],
-                            kn, pair_ok, h->sc_tparams, pr, px, lds, grid, nhwc);
-        }
-        if (!ok && nhwc && kn.band && kn.wave != 2 && kn.strip != 2 && cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok) {
-            int nw = 0;
-            bool dd = false;
-            ok = plan_band(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f], kn,
-                           h->sc_tparams, px, dd, nw, lds, 4);
-        }
-        if (!ok && kn.wave && (!nhwc || nhwc_wave_ok)) {
-            WParams w{};
-            bool reuse = false;
-            ok = plan_wave(f, g, DW, DH, count[f], cfg->out_dtype, h->n_cu, h->sc_xt.data(), h->sc_yt.data(), x0_mask[f], kn,
-                           w, px, reuse, lds, grid, nhwc ? 4 : 0) &&
-                 (reuse || kn.wave == 2 || nhwc);
-        }
+        const bool ok = plan_group(f, h->sc_xt.data(), h->sc_yt.data(), pair_ok).family != 0;
         memcpy(h->nhwc_key[f], key, sizeof(key));
         h->nhwc_ok[f] = ok ? 1 : 0;
         return ok;
@@ -4796,6 +4680,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     QParams qp[4];
     int qlds[4] = {0, 0, 0, 0}, qbase[4] = {1, 1, 1, 1}, qrec[4] = {0, 0, 0, 0};
     int64_t qslots[4] = {0, 0, 0, 0};
+    const void* qfn[4] = {nullptr, nullptr, nullptr, nullptr};
     bool any_generic = false, any_roi = false;
     for (int f = 0; f < 4; f++) {
         path[f] = kPathNone;
@@ -4807,7 +4692,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         else if (half && uniform[f] && kn.rows) path[f] = planned_uniform_ok(f) ? kPathUniform : kPathGeneric;
         else if (uniform[f] && kn.rows) path[f] = kPathUniform;
         else if (kn.roi && plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_cw[f]), count[f], h->n_cu,
-                                    kn, qp[f], qbase[f], qlds[f], qslots[f])) path[f] = kPathRoi;
+                                    kn, qp[f], qbase[f], qlds[f], qslots[f], qfn[f])) path[f] = kPathRoi;
         else path[f] = kPathGeneric;
         any_generic |= path[f] == kPathGeneric;
         any_roi |= path[f] == kPathRoi;
@@ -4956,7 +4841,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
             // two rounds and were retired in round 5.)
             const QParams& q = qp[f];
             const int base = qbase[f];
-            const int pxr = (kn.roi_px == 4 || kn.roi_px == 2) && DW % kn.roi_px == 0 ? kn.roi_px : 1;
+            const int pxr = roi_px(kn.roi_px, DW, false);
             const int rcap = std::max(1, ((kRoiK / pxr) * kThreads) / (DW / pxr));
             int nu = 0;
             if (base == 1) {
@@ -5111,8 +4996,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
             q.prio = kn.prio;
             const int64_t grid = qrec[f];
             if (grid > 0x7FFFFFFF) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: too many tiles");
-            hipError_t e = launch_roi(f, cfg->out_dtype, kn.roi_px, 2, q, (int)grid, qlds[f], h->stream);
-            if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+            if (int rc = launch_kernel(qfn[f], dim3((unsigned)grid), dim3(kThreads), qlds[f], h->stream, &q, true)) return rc;
             launches++; kmask |= EVAM_KERNEL_ROI;
             continue;
         }
@@ -5120,198 +5004,49 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
             const Geom& g0 = geo[rep[f]];
             const XTab* xt_d = reinterpret_cast<const XTab*>(d_block + tab_off[f]);
             const YTab* yt_d = reinterpret_cast<const YTab*>(xt_d + DW);
-            const int per_launch = std::min(count[f], kArgItems);
-            if (kn.strip && kn.wave != 2 && (!nhwc || cfg->out_dtype == EVAM_DTYPE_F32)) {
-                TParams* tp = &h->sc_tparams;
-                int pr = 0, spx = 0, lds = 0, grid = 0;
-                const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
-                const bool pair_ok = strip_pair_ok(f);
-                if (plan_strip(f, g0, DW, DH, count[f], cfg->out_dtype, h->n_cu, hx, reinterpret_cast<const YTab*>(hx + DW),
-                               x0_mask[f], kn, pair_ok, *tp, pr, spx, lds, grid, nhwc)) {
-                    tp->lut = lut_d;
-                    tp->dst = dst->data;
-                    tp->slot_offset = slot_offset;
-                    tp->slot_stride = slot_stride;
-                    tp->color_rgb = color_rgb;
-                    tp->fill = fill;
-                    tp->prio = kn.prio;
-                    for (int m0 = mfirst[f]; m0 < mfirst[f + 1]; m0 += kArgItems) {
-                        const int nm = std::min(kArgItems, mfirst[f + 1] - m0);
-                        fill_args(tp->items, m0, nm);
-                        // grid (tile column, tile row, item), dispatched in that order (the C2 data movement in
-                        // the strip pattern takes 1.7 us longer with each XCD on its own run of tiles,
-                        // profiles/r03c_strip_bw.txt)
-                        const dim3 gr((unsigned)tp->tiles_x, (unsigned)((DH + tp->TH - 1) / tp->TH), (unsigned)nm);
-                        hipError_t e = nhwc ? launch_strip_nhwc(f, pr, spx, *tp, gr, lds, h->stream)
-                                            : launch_strip(f, cfg->out_dtype, pr, spx, *tp, gr, lds, h->stream);
-                        if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-                        launches++; kmask |= EVAM_KERNEL_STRIP;
-                    }
-                    (void)grid;
-                    continue;
-                }
-            }
-            if (kn.band && kn.wave != 2 && kn.strip != 2 && !half &&
-                (!nhwc || (cfg->out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok))) {
-                TParams* tp = &h->sc_tparams;
-                int bpx = 0, nw = 0, lds = 0;
-                bool dd = false;
-                const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
-                if (plan_band(f, g0, DW, DH, count[f], cfg->out_dtype, h->n_cu, hx, reinterpret_cast<const YTab*>(hx + DW),
-                              x0_mask[f], kn, *tp, bpx, dd, nw, lds, nhwc ? 4 : 0)) {
-                    tp->lut = lut_d;
-                    tp->dst = dst->data;
-                    tp->slot_offset = slot_offset;
-                    tp->slot_stride = slot_stride;
-                    tp->color_rgb = color_rgb;
-                    tp->fill = fill;
-                    tp->prio = kn.prio;
-                    tp->ahead = std::max(0, kn.band_ahead);
-                    for (int m0 = mfirst[f]; m0 < mfirst[f + 1]; m0 += kArgItems) {
-                        const int nm = std::min(kArgItems, mfirst[f + 1] - m0);
-                        fill_args(tp->items, m0, nm);
-                        tp->units = nm * tp->tiles_per_item;
-                        const dim3 gr((unsigned)tp->tiles_x, (unsigned)((DH + tp->TH - 1) / tp->TH), (unsigned)nm);
-                        hipError_t e = nhwc ? launch_band_nhwc(f, dd, *tp, gr, nw, lds, h->stream)
-                                            : launch_band(f, cfg->out_dtype, bpx, dd, *tp, gr, nw, lds, h->stream);
-                        if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-                        launches++; kmask |= EVAM_KERNEL_BAND;
-                    }
-                    continue;
-                }
-            }
-            if (kn.wave && (!nhwc || nhwc_wave_ok)) {
-                WParams w{};
-                int px = 0, lds = 0, grid = 0;
-                bool reuse = false;
-                const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
-                // The wave kernel wins where consecutive output rows share source rows (vertical
-                // upscale: REUSE); for downscales the staged kernel's deeper shared staging is faster.
-                if (plan_wave(f, g0, DW, DH, count[f], cfg->out_dtype, h->n_cu, hx,
-                              reinterpret_cast<const YTab*>(hx + DW), x0_mask[f], kn, w, px, reuse, lds, grid,
-                              nhwc ? 4 : 0) &&
-                    (reuse || kn.wave == 2 || nhwc)) {
-                    w.ox = g0.ox;
-                    w.rw = g0.rw;
-                    w.lut = lut_d;
-                    w.xtab = xt_d;
-                    w.ytab = yt_d;
-                    w.dst = dst->data;
-                    w.slot_offset = slot_offset;
-                    w.slot_stride = slot_stride;
-                    w.color_rgb = color_rgb;
-                    w.fill = fill;
-                    for (int m0 = mfirst[f]; m0 < mfirst[f + 1]; m0 += kArgItems) {
-                        const int n = std::min(kArgItems, mfirst[f + 1] - m0);
-                        fill_args(w.items, m0, n);
-                        hipError_t e = nhwc ? launch_wave_nhwc(f, cfg->out_dtype, reuse, w, n * w.tiles_per_item, lds, h->stream)
-                                            : launch_wave(f, cfg->out_dtype, px, reuse, w, n * w.tiles_per_item, lds, h->stream);
-                        if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-                        launches++; kmask |= EVAM_KERNEL_WAVE;
-                    }
-                    continue;
-                }
-            }
-            if (!nhwc && !half) {
-            // Tile width: the widest of 256 / 128 columns whose staged row segment (the exact widest footprint of
-            // any tile and crop origin of this group) fits the kernel's 1 KB slot.
             const XTab* hx = reinterpret_cast<const XTab*>(h->h_block.data() + tab_off[f]);
-            auto seg_bytes = [&](int tw) {
-                int mY = 0, mC = 0;
-                wave_segments(f, g0.ox, g0.rw, DW, hx, x0_mask[f], tw, mY, mC);
-                return 16 * std::max(1, std::max(mY, mC));
+            const LaunchPlan k = plan_group(f, hx, reinterpret_cast<const YTab*>(hx + DW), strip_pair_ok(f));
+            if (!k.family)  // the early decision asked the same function the same question
+                return fail(EVAM_PP_ERR_HIP, "evam_pp_run: the interleaved or 16-bit group's plan did not repeat (internal error)");
+            auto common = [&](auto& p) {
+                p.lut = lut_d;
+                p.dst = dst->data;
+                p.slot_offset = slot_offset;
+                p.slot_stride = slot_stride;
+                p.color_rgb = color_rgb;
+                p.fill = fill;
             };
-            int nsegx = 0;
-            if (kn.staged)
-                for (int n : {4, 2}) {  // (64 columns would need R % 4 == 0: the row kernel serves those)
-                    if (seg_bytes(64 * n) <= kSlot) { nsegx = n; break; }
-                }
-            if (nsegx && kn.nsegx > 0 && kn.nsegx < nsegx && 2 % (4 / kn.nsegx) == 0) nsegx = kn.nsegx;
-            if (nsegx) {
-                // Pipeline shape: R output rows per group, NBUF staging buffers (NBUF - 1 groups of DMA in
-                // flight).
-                int R = kn.stage_r > 0 ? kn.stage_r : 2, nbuf = 2;
-                bool shape_ok = false;
-                for (const StagedShape& ss : kStagedShapes) shape_ok |= ss.R == R && ss.nbuf == nbuf;
-                if (!shape_ok || !staged_valid(nsegx, R)) { R = 2; nbuf = 2; }
-                SParams sp{};
-                sp.ox = g0.ox;
-                sp.rw = g0.rw;
-                sp.lut = lut_d;
-                sp.xtab = xt_d;
-                sp.ytab = yt_d;
-                sp.dst = dst->data;
-                sp.slot_offset = slot_offset;
-                sp.slot_stride = slot_stride;
-                sp.DW = DW; sp.DH = DH;
-                const int tw = 64 * nsegx;
-                sp.tiles_x = (DW + tw - 1) / tw;
-                // ~4096 pixels per workgroup, but short enough tiles that small batches still put
-                // 8 workgroups on every CU (a whole clip-ring step is only 32 x 224 x 224 pixels).
-                // At most 16 rows: C4 (tw 128) runs 3-7 % faster at 16 than at 32 (profiles/r01ad_sweep_th*.txt).
-                int th = std::max(2, std::min(16, 4096 / tw));
-                const int64_t cols = (int64_t)per_launch * sp.tiles_x;
-                const int64_t want = 8 * (int64_t)h->n_cu;
-                if (cols * ((DH + th - 1) / th) < want) th = (int)std::max<int64_t>(2, cols * DH / want);
-                sp.TH = std::max(1, std::min(std::min(DH, 64), kn.th > 0 ? kn.th : th));  // <= 64: lane-held rows
-                sp.TH = std::min(64, (sp.TH + R - 1) / R * R);
-                sp.tiles_per_item = sp.tiles_x * ((DH + sp.TH - 1) / sp.TH);
-                const int np = f == kI420 ? 3 : (f == kNV12 ? 2 : 1);
-                sp.offBuf = cfg->out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
-                sp.slot_bytes = seg_bytes(tw);  // <= the kernel's SLOT_MAX (tile choice above)
-                sp.buf_bytes = 2 * R * np * sp.slot_bytes;
-                sp.ntcol = sp.tiles_x <= kTCols ? sp.tiles_x : 0;
-                for (int c = 0; c < sp.ntcol; c++) {
-                    const int Xv0 = std::max(c * tw, g0.ox), Xv1 = std::min(std::min(c * tw + tw, DW), g0.ox + g0.rw) - 1;
-                    sp.tcol[c] = Xv0 <= Xv1 ? int2{hx[Xv0].s0, hx[Xv1].s1} : int2{-1, -1};
-                }
-                sp.color_rgb = color_rgb;
-                sp.fill = fill;
-                const int lds = sp.offBuf + nbuf * sp.buf_bytes;
-                for (int m0 = mfirst[f]; m0 < mfirst[f + 1]; m0 += kArgItems) {
-                    const int n = std::min(kArgItems, mfirst[f + 1] - m0);
-                    fill_args(sp.items, m0, n);
-                    const int64_t grid = (int64_t)n * sp.tiles_per_item;
-                    if (grid > 0x7FFFFFFF) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: too many tiles");
-                    // XCD-contiguous tiles: C2 -1.4 %, C4 -3 % kernel time; a grid of one workgroup round or
-                    // less (C5) gains nothing (profiles/r01ae_sweep_xcd.txt). EVAM_PP_XCD=0/1 forces it.
-                    sp.xcd_remap = kn.xcd >= 0 ? kn.xcd : (int)(grid >= 8 * (int64_t)h->n_cu);
-                    hipError_t e = launch_staged(f, cfg->out_dtype, nsegx, R, nbuf, sp, (int)grid, lds, h->stream);
-                    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-                    launches++; kmask |= EVAM_KERNEL_STAGED;
-                }
-                continue;
+            auto tables = [&](auto& p) {
+                common(p);
+                p.ox = g0.ox;
+                p.rw = g0.rw;
+                p.xtab = xt_d;
+                p.ytab = yt_d;
+            };
+            TParams& tp = h->sc_tparams;
+            switch (k.family) {
+            case EVAM_KERNEL_STRIP: common(tp); tp.prio = kn.prio; break;
+            case EVAM_KERNEL_BAND: common(tp); tp.prio = kn.prio; tp.ahead = std::max(0, kn.band_ahead); break;
+            case EVAM_KERNEL_WAVE: tables(up.w); break;
+            case EVAM_KERNEL_STAGED: tables(up.s); break;
+            default: tables(up.r); break;
             }
-            const RowCfg rc = choose_row_tiles(DW, DH, kn);
-            RParams r{};
-            r.ox = g0.ox;
-            r.rw = g0.rw;
-            r.lut = lut_d;
-            r.xtab = xt_d;
-            r.ytab = yt_d;
-            r.dst = dst->data;
-            r.slot_offset = slot_offset;
-            r.slot_stride = slot_stride;
-            r.DW = DW; r.DH = DH;
-            r.TW = rc.TW; r.TH = rc.TH;
-            r.tiles_x = (DW + rc.TW - 1) / rc.TW;
-            r.tiles_per_item = r.tiles_x * ((DH + rc.TH - 1) / rc.TH);
-            r.nsegx = rc.TW / 64;
-            r.color_rgb = color_rgb;
-            r.fill = fill;
-            const int lds = cfg->out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
             for (int m0 = mfirst[f]; m0 < mfirst[f + 1]; m0 += kArgItems) {
                 const int n = std::min(kArgItems, mfirst[f + 1] - m0);
-                fill_args(r.items, m0, n);
-                const int64_t grid = (int64_t)n * r.tiles_per_item;
+                fill_args(k.items, m0, n);
+                const int64_t grid = (int64_t)n * k.tiles_per_item;
                 if (grid > 0x7FFFFFFF) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: too many tiles");
-                hipError_t e = launch_rows(f, cfg->out_dtype, r, (int)grid, lds, h->stream);
-                if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
-                launches++; kmask |= EVAM_KERNEL_ROWS;
+                if (k.family == EVAM_KERNEL_BAND) tp.units = (int)grid;
+                // XCD-contiguous tiles: C2 -1.4 %, C4 -3 % kernel time; a grid of one workgroup round or
+                // less (C5) gains nothing (profiles/r01ae_sweep_xcd.txt). EVAM_PP_XCD=0/1 forces it.
+                if (k.family == EVAM_KERNEL_STAGED) up.s.xcd_remap = kn.xcd >= 0 ? kn.xcd : (int)(grid >= 8 * (int64_t)h->n_cu);
+                const dim3 gr = k.gy ? dim3((unsigned)k.gx, (unsigned)k.gy, (unsigned)n) : dim3((unsigned)grid);
+                if (int rc = launch_kernel(k.fn, gr, dim3((unsigned)k.block), k.lds, h->stream, k.params,
+                                           k.family == EVAM_KERNEL_STAGED))
+                    return rc;
+                launches++; kmask |= k.family;
             }
             continue;
-            }
-            return fail(EVAM_PP_ERR_HIP, "evam_pp_run: the interleaved or 16-bit group's plan did not repeat (internal error)");
         }
         const ItemDesc* items_d = reinterpret_cast<const ItemDesc*>(d_block + desc_off) + first[f];
         const TileCfg t = choose_tiles(DW, DH, cfg->out_dtype, kn);
@@ -5333,21 +5068,9 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         p.offCol = t.offCol; p.offRow = t.offRow;
         p.color_rgb = color_rgb;
         p.fill = fill;
-        const int lds = t.lds;
-        if (lds > 64 * 1024 && !nhwc) {
-            hipError_t e = hipSuccess;
-            switch (f * 3 + out_kind(cfg->out_dtype)) {
-#define SETATTR(F, O) case F * 3 + O: e = hipFuncSetAttribute((const void*)evam_pp_kernel<F, O>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); break;
-                SETATTR(kNV12, 0) SETATTR(kNV12, 1) SETATTR(kI420, 0) SETATTR(kI420, 1)
-                SETATTR(kBGRX, 0) SETATTR(kBGRX, 1) SETATTR(kBGR, 0) SETATTR(kBGR, 1)
-                SETATTR(kNV12, 2) SETATTR(kI420, 2) SETATTR(kBGRX, 2) SETATTR(kBGR, 2)
-#undef SETATTR
-            }
-            if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        }
-        hipError_t e = nhwc ? launch_nhwc(f, cfg->out_dtype, p, (int)n_tiles, lds, h->stream)
-                            : launch(f, cfg->out_dtype, p, (int)n_tiles, lds, h->stream);
-        if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+        if (int rc = launch_kernel(generic_kernel(f, cfg->out_dtype, nhwc), dim3((unsigned)n_tiles), dim3(kThreads), t.lds,
+                                   h->stream, &p, true))
+            return rc;
         launches++; kmask |= EVAM_KERNEL_GENERIC;
     }
     if (any_roi) {
@@ -5548,8 +5271,10 @@ int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, cons
     QParams q{};
     int base = 1, lds = 0;
     int64_t slots = 0;
+    const void* fn = nullptr;
     HIP_TRY(hipSetDevice(h->device));
-    if (!plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_w), cap, h->n_cu, kn, q, base, lds, slots, true))
+    if (!plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_w), cap, h->n_cu, kn, q, base, lds, slots, fn,
+                  true))
         return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: %dx%d output from %d-wide sources is not planned by the ROI kernel", who, DW,
                     DH, max_w);
     const int64_t units = (int64_t)cap * base;
@@ -5592,8 +5317,7 @@ int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, cons
     q.color_rgb = cfg->color_order == EVAM_COLOR_RGB;
     q.fill = (uint32_t)cfg->fill[0] | ((uint32_t)cfg->fill[1] << 8) | ((uint32_t)cfg->fill[2] << 16);
     q.prio = kn.prio;
-    e = launch_roi_dev(f, cfg->out_dtype, kn.roi_px, q, (int)units, lds, h->stream);
-    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    if (int rc = launch_kernel(fn, dim3((unsigned)units), dim3(kThreads), lds, h->stream, &q, true)) return rc;
     if (h->opt_timing) HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->timed = h->opt_timing != 0;
     h->stats.n_items = cap;

@@ -155,10 +155,11 @@ def test_device_list_convert_bit_exact(evam, O, coracle, gpu, fmt, out, resize):
     info = make_info(evam, out, resize, rgb)
     pp = evam.HipPreProcessor(device=0)
     try:
-        # (output size, rects, cap, slot offset, slot stride); 256x160 is three row tiles per entry
+        # (output size, rects, cap, slot offset, slot stride); 256x160 is three row tiles per entry; 75x40 is an odd
+        # width: one pixel per lane (evam_pp_roi<.., 1, 2, DEV>), where every even width takes two
         plans = [((24, 24), 40, 48, 1, 2), ((72, 72), 40, 48, 0, 1)]
         if resize == "plain":
-            plans.append(((256, 160), 9, 12, 2, 1))
+            plans += [((256, 160), 9, 12, 2, 1), ((75, 40), 3, 4, 0, 1)]
         for (DW, DH), n, cap, off, stride in plans:
             rects = make_rects(rng, SRC_SIZES, n)
             shape = (off + cap * stride, 3, DH, DW)

@@ -39,6 +39,27 @@ VARIANTS = {
     "band_dd1": ("BAND", {"EVAM_PP_BAND": "2", "EVAM_PP_STRIP": "0", "EVAM_PP_BAND_DD": "1"}, "band"),
     "band_dd0": ("BAND", {"EVAM_PP_BAND": "2", "EVAM_PP_STRIP": "0", "EVAM_PP_BAND_DD": "0"}, "band"),
 }
+# Variants that run only the EXTRA cases below: with them every instantiation of the kernel tables that the API and
+# the knobs can reach is dispatched by some test of the suite.
+_STAGED = VARIANTS["staged"][1]
+EXTRA_VARIANTS = {
+    "wave_px2": ("WAVE", {"EVAM_PP_WAVE": "2", "EVAM_PP_PX": "2"}, "up"),
+    "wave_noreuse": ("WAVE", {"EVAM_PP_WAVE": "2", "EVAM_PP_REUSE": "0"}, "up"),
+    "wave_noreuse_px1": ("WAVE", {"EVAM_PP_WAVE": "2", "EVAM_PP_REUSE": "0", "EVAM_PP_PX": "1"}, "up"),
+    "wave_noreuse_px2": ("WAVE", {"EVAM_PP_WAVE": "2", "EVAM_PP_REUSE": "0", "EVAM_PP_PX": "2"}, "up"),
+    "wave_noreuse_px4": ("WAVE", {"EVAM_PP_WAVE": "2", "EVAM_PP_REUSE": "0", "EVAM_PP_PX": "4"}, "up"),
+    "strip_px2_paired": ("STRIP", {"EVAM_PP_STRIP": "2", "EVAM_PP_STRIP_PX": "2"}, "down2_packed"),
+    "staged_r1": ("STAGED", dict(_STAGED, EVAM_PP_STAGE_R="1"), "down"),
+    "staged_nsegx2": ("STAGED", dict(_STAGED, EVAM_PP_NSEGX="2"), "down"),
+}
+EXTRA = ([(v, fmt, "f16") for v in ("wave_noreuse_px1", "wave_noreuse_px2", "wave_noreuse_px4") for fmt in FORMATS] +
+         [("wave_px2", fmt, "f16") for fmt in ("NV12", "I420", "BGR")] +
+         [("wave_noreuse", fmt, "nhwc_f32") for fmt in ("NV12", "I420", "BGRX")] +
+         [(v, fmt, "nhwc_f32") for v in ("strip_px1_unpaired", "strip_px2_unpaired") for fmt in ("NV12", "I420")] +
+         [("strip_px2_unpaired", "BGRX", "nhwc_f32")] +
+         [("strip_px2_paired", "BGRX", out) for out in ("u8", "f32", "f16")] +
+         [("staged_r1", "BGRX", "u8"), ("staged_r1", "BGRX", "f32"), ("staged_nsegx2", "I420", "f32")])
+VARIANTS_ALL = dict(VARIANTS, **EXTRA_VARIANTS)
 
 
 def geometry(geo, fmt, out):
@@ -56,12 +77,14 @@ def geometry(geo, fmt, out):
     src = {"NV12": (640, 360), "I420": (640, 360), "BGRX": (160, 90), "BGR": (240, 136)}[fmt]
     if geo == "down2" and fmt in ("NV12", "I420"):
         src = (320, 180)  # a 128-column strip's rows stay under the 512 B a paired tap takes
+    if geo == "down2_packed":
+        src = (96, 180)  # ... and those of 4-byte pixels: 1:1 across, 96 columns x 4 B
     return src, (94 if odd and geo == "down" else 96, 96), "no-aspect-ratio"
 
 
 def unsupported(variant, fmt, out):
     """Why the family has no instantiation for the combination (None: it has one)."""
-    family = VARIANTS[variant][0]
+    family = VARIANTS_ALL[variant][0]
     if family == "STRIP" and fmt == "BGR":
         return "the strip kernel is built for NV12, I420 and BGRX"
     if family == "BAND" and fmt in ("BGRX", "BGR"):
@@ -81,14 +104,17 @@ def family_cases():
                 why = unsupported(variant, fmt, out)
                 cases.append(pytest.param(variant, fmt, out, id=f"{variant}-{fmt}-{out}",
                                           marks=[pytest.mark.skip(reason=why)] if why else []))
+    for variant, fmt, out in EXTRA:
+        assert unsupported(variant, fmt, out) is None
+        cases.append(pytest.param(variant, fmt, out, id=f"{variant}-{fmt}-{out}"))
     return cases
 
 
 def make_out(torch, out, shape, gpu):
     if out == "f16":
         return half_full(torch, shape, "f16", gpu)
-    t = torch.empty(shape, dtype=torch.float32 if out == "f32" else torch.uint8, device=gpu,
-                    memory_format=torch.channels_last if out == "nhwc_u8" else torch.contiguous_format)
+    t = torch.empty(shape, dtype=torch.float32 if out in ("f32", "nhwc_f32") else torch.uint8, device=gpu,
+                    memory_format=torch.channels_last if out.startswith("nhwc") else torch.contiguous_format)
     t.fill_(7)
     return t
 
@@ -110,14 +136,14 @@ def test_family_layouts(evam, O, coracle, gpu, variant, fmt, out, monkeypatch):
     launch ran on the family the case names."""
     import torch
 
-    family, env, geo = VARIANTS[variant]
+    family, env, geo = VARIANTS_ALL[variant]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     (W, H), (DW, DH), resize = geometry(geo, fmt, out)
     rng = np.random.default_rng(zlib.crc32(repr((variant, fmt, out)).encode()))
     frames = [O.random_frame(rng, fc(O, fmt), W, H, pattern=p) for p in ("uniform", "gradient", "uniform")]
     imgs, hosts = SL.lay_out_all(evam, torch, O, frames, ITEM_KINDS, rng, gpu)
-    rgb = (FORMATS.index(fmt) + OUTPUTS.index(out)) % 2 == 1
+    rgb = (FORMATS.index(fmt) + (OUTPUTS + ["nhwc_f32"]).index(out)) % 2 == 1
     dtype = "u8" if out in ("u8", "nhwc_u8") else "f32"
     info = evam.PreProcInfo(resize=resize, placement="center", fill=(5, 50, 250), color_space="RGB" if rgb else "BGR",
                             precision="FP16" if out == "f16" else None, **(NORM if dtype == "f32" else {}))
@@ -168,13 +194,14 @@ def layout_rois(rng):
     return rois
 
 
-@pytest.mark.parametrize("dst,dtype", [((72, 72), "f32"), ((64, 36), "u8")])
+@pytest.mark.parametrize("dst,dtype", [((72, 72), "f32"), ((64, 36), "u8"), ((72, 72), "f16")])
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("variant", sorted(ROI_ENVS))
 def test_roi_layouts(evam, O, coracle, gpu, variant, fmt, dst, dtype, monkeypatch):
     """32 ROIs (partly outside, 1 x 1, whole frames) over three sources of different sizes, each in its own layout:
-    the ROI kernel with its records built on the device path and the host path and at every pixels-per-lane setting,
-    and the generic kernel, each asserted to have run."""
+    the ROI kernel with its records built on the device path and the host path and at every pixels-per-lane setting
+    (fp16 too: the 2-byte instantiations at 1, 2 and 4 pixels per lane), and the generic kernel, each asserted to
+    have run."""
     import torch
 
     family, env = ROI_ENVS[variant]
@@ -186,11 +213,11 @@ def test_roi_layouts(evam, O, coracle, gpu, variant, fmt, dst, dtype, monkeypatc
     imgs, hosts = SL.lay_out_all(evam, torch, O, frames, ROI_KINDS, rng, gpu)
     rois = layout_rois(rng)
     info = evam.PreProcInfo(resize="aspect-ratio", placement="center", fill=(3, 60, 200), color_space="RGB",
-                            **(NORM if dtype == "f32" else {}))
+                            precision="FP16" if dtype == "f16" else None, **(NORM if dtype != "u8" else {}))
     n = len(rois)
     shape = (n + 1, 3, dst[1], dst[0])
-    ref, _ = run_oracle(O, coracle, hosts, shape, dtype, info, rois=rois)
-    got = torch.full(shape, 7, dtype=torch.float32 if dtype == "f32" else torch.uint8, device=gpu)
+    ref, _ = run_oracle(O, coracle, hosts, shape, "u8" if dtype == "u8" else "f32", info, rois=rois)
+    got = make_out(torch, dtype, shape, gpu)
     pp = evam.HipPreProcessor(device=0)
     try:
         pp.convert(imgs, got, info, rois=[evam.Roi(*r) for r in rois])
@@ -201,7 +228,7 @@ def test_roi_layouts(evam, O, coracle, gpu, variant, fmt, dst, dtype, monkeypatc
     what = f"roi layouts {variant} {fmt} -> {dst} {dtype}"
     assert k == getattr(evam.native, "KERNEL_" + family), f"{what}: kernel family bits {k:#x}, not {family}"
     assert (ref[n] == 7).all()
-    assert_same(got.cpu().numpy(), ref, what)
+    compare(torch, dtype, got, ref, what)
 
 
 # ---- the default planner ----------------------------------------------------------------------------------------
