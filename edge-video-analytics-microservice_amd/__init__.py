@@ -9,14 +9,15 @@ After the first import the package is also reachable as ``evam_amd`` (``sys.modu
 
 Scope: decoded NV12/I420/BGRx/BGR frames -> colour conversion -> INTER_LINEAR /
 letterbox / central-crop resize -> ROI crop-resize -> normalisation -> NCHW (planar) or NHWC (interleaved:
-``torch.channels_last`` tensors, ``HipPreProcessor.export_bgr`` frames) batch packing, and baseline JPEG encoding of the published frame
-(``HipPreProcessor.encode_jpeg``), as hand-written HIP kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
+``torch.channels_last`` tensors, ``HipPreProcessor.export_bgr`` frames) batch packing, baseline JPEG encoding of the published frame
+(``HipPreProcessor.encode_jpeg``) and baseline JPEG decoding of source frames (``HipPreProcessor.decode_jpeg``), as
+hand-written HIP kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
 """
 import sys as _sys
 
 from ._native import PreProcError, jpeg_bound, jpeg_header, load_library  # noqa: F401
-from .preproc import (DeviceRoiList, HipPreProcessor, Image, ImageBatch, PreProcInfo, Roi, RoiBatch,  # noqa: F401
-                      Transform, create_preprocessor, output_dtype, plane_layout, tensor_layout)
+from .preproc import (DeviceRoiList, HipPreProcessor, Image, ImageBatch, JpegInfo, PreProcInfo, Roi,  # noqa: F401
+                      RoiBatch, Transform, create_preprocessor, jpeg_info, output_dtype, plane_layout, tensor_layout)
 from . import _native as native  # noqa: F401
 from . import streams  # noqa: F401
 from . import postproc  # noqa: F401

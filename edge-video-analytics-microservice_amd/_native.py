@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "evam_pp_linear_table", "evam_pp_norm_table",
     "evam_pp_jpeg_header", "evam_pp_encode_jpeg",
     "evam_pp_ssd_rois", "evam_pp_ssd_rois_host", "evam_pp_run_device_rois",
+    "evam_pp_jpeg_info", "evam_pp_decode_jpeg", "evam_pp_decode_jpeg_host",
 )
 # ... and the one that returns size_t (tests/test_abi.py reads the header's int / void / const char* declarations)
 EXPORTED_SYMBOLS_SIZE_T = ("evam_pp_jpeg_bound",)
@@ -101,16 +102,24 @@ class EvamStats(ctypes.Structure):
                 ("n_launches", c_i32), ("last_kernel_ms", ctypes.c_float), ("kernels", ctypes.c_uint32)]
 
 
+class EvamJpegInfo(ctypes.Structure):
+    """``evam_jpeg_info``: what ``evam_pp_jpeg_info`` reads from a file's markers."""
+
+    _fields_ = [("width", c_i32), ("height", c_i32), ("components", c_i32), ("h_samp", c_i32), ("v_samp", c_i32),
+                ("restart_interval", c_i32), ("scan_offset", ctypes.c_uint32)]
+
+
 # evam_pp_stats.kernels bits (include/evam_pp.h evam_kernel_family)
 KERNEL_GENERIC, KERNEL_ROWS, KERNEL_STAGED, KERNEL_WAVE = 1, 2, 4, 8
 KERNEL_STRIP, KERNEL_BAND, KERNEL_ROI = 16, 32, 64
 KERNEL_JPEG = 128
+KERNEL_JPEG_DEC = 256
 
 JPEG_HEADER_LEN = 623  # SOI .. SOS of every file evam_pp_encode_jpeg writes
 
 
 STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32,
-                EvamRoiList: 24}
+                EvamRoiList: 24, EvamJpegInfo: 28}
 
 _LIB = None
 
@@ -163,6 +172,13 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_run_device_rois.argtypes = [vp, P(EvamImage), ctypes.c_int, P(EvamRoiList), P(EvamPreproc),
                                             P(EvamTensor), vp]
     lib.evam_pp_run_device_rois.restype = ctypes.c_int
+    lib.evam_pp_jpeg_info.argtypes = [vp, ctypes.c_size_t, P(EvamJpegInfo)]
+    lib.evam_pp_jpeg_info.restype = ctypes.c_int
+    dec = [P(vp), P(ctypes.c_size_t), ctypes.c_int, P(EvamImage), vp]
+    lib.evam_pp_decode_jpeg.argtypes = [vp] + dec
+    lib.evam_pp_decode_jpeg.restype = ctypes.c_int
+    lib.evam_pp_decode_jpeg_host.argtypes = dec
+    lib.evam_pp_decode_jpeg_host.restype = ctypes.c_int
     return lib
 
 
@@ -211,6 +227,61 @@ def jpeg_bound(width: int, height: int) -> int:
     if n == 0:
         raise PreProcError(ERR_INVALID_ARG, f"jpeg_bound: bad frame size {width}x{height}")
     return n
+
+
+def _file_bytes(file) -> bytes:
+    if isinstance(file, bytes):
+        return file
+    if isinstance(file, (bytearray, memoryview)):
+        return bytes(file)
+    raise PreProcError(ERR_INVALID_ARG, f"a JPEG file is bytes, bytearray or memoryview, not {type(file).__name__}")
+
+
+def jpeg_file_arrays(files):
+    """``(kept bytes objects, const uint8_t*[n], size_t[n])`` of a sequence of JPEG files for the decode calls."""
+    keep = [_file_bytes(f) for f in files]
+    n = len(keep)
+    ptrs = (ctypes.c_void_p * max(n, 1))()
+    lens = (ctypes.c_size_t * max(n, 1))()
+    for i, b in enumerate(keep):
+        ptrs[i] = ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p)
+        lens[i] = len(b)
+    return keep, ptrs, lens
+
+
+def jpeg_info_struct(file) -> EvamJpegInfo:
+    """``evam_pp_jpeg_info`` of one file (bytes-like). Raises PreProcError for a refused file. Host-only."""
+    lib = load_library()
+    b = _file_bytes(file)
+    info = EvamJpegInfo()
+    check(lib, lib.evam_pp_jpeg_info(ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p), len(b), ctypes.byref(info)))
+    return info
+
+
+def decode_jpeg_host(files, fourcc: int = FOURCC_BGRX, pad: int = 0):
+    """``evam_pp_decode_jpeg_host``: decode files of one geometry on the host.
+
+    Returns ``(uint8 [n, H, pitch] array, pitch, int32 [n] status)``; the pitch is the row bytes rounded up to 16 plus
+    ``pad`` (a multiple of 16), and the bytes behind each row's pixels keep the value 0xA5. Host-only."""
+    import numpy as np
+
+    lib = load_library()
+    keep, ptrs, lens = jpeg_file_arrays(files)
+    n = len(keep)
+    info = jpeg_info_struct(keep[0]) if n else EvamJpegInfo()
+    bpp = 3 if fourcc == FOURCC_BGR else 4
+    pitch = (info.width * bpp + 15) // 16 * 16 + int(pad)
+    raw = np.full(n * info.height * pitch + 16, 0xA5, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    buf = raw[off:off + n * info.height * pitch].reshape(n, info.height, pitch)
+    imgs = (EvamImage * max(n, 1))()
+    for i in range(n):
+        imgs[i].fourcc, imgs[i].width, imgs[i].height = fourcc, info.width, info.height
+        imgs[i].pitch[0] = pitch
+        imgs[i].planes[0] = buf[i].ctypes.data
+    status = np.full(max(n, 1), 0x7FFFFFFF, np.int32)
+    check(lib, lib.evam_pp_decode_jpeg_host(ptrs, lens, n, imgs, status.ctypes.data))
+    return buf, pitch, status[:n]
 
 
 def transforms_array(transforms, n: int):

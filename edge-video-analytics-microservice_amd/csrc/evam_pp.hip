@@ -47,6 +47,7 @@
 #include "evam_geom.h"
 #include "evam_rings.h"
 #include "evam_clip_simd.h"
+#include "evam_jpeg_dec.h"
 
 namespace {
 
@@ -4175,6 +4176,19 @@ using DescRing = DescRingT<HipRings>;
 using PinRing = PinRingT<HipRings>;
 
 #include "evam_jpeg_kernels.h"
+#include "evam_jpeg_dec_kernels.h"
+
+// evam_pp_decode_jpeg: device scratch (grown on demand, reused) and the pinned staging of the file bytes.
+enum { kJdUp = 0, kJdStream, kJdFirst, kJdSlots, kJdCoef, kJdPlanes, kJdCount };
+struct JdecScratch {
+    void* buf[kJdCount] = {};
+    size_t cap[kJdCount] = {};
+    uint8_t* pin = nullptr;        // pinned staging: tables, output descriptors, file bytes of one call
+    size_t pin_cap = 0;
+    hipEvent_t pin_ev = nullptr;   // recorded behind the copy out of pin
+    bool pin_busy = false;
+    std::vector<JdecFile> parsed;  // per-call scratch
+};
 
 }  // namespace
 
@@ -4227,6 +4241,7 @@ struct evam_pp {
     int nhwc_key[4][16] = {};      // per format: what the last interleaved uniform group's choice depended on
     int nhwc_ok[4] = {-1, -1, -1, -1};  // ... and the choice: 1 strip / wave kernel, 0 generic kernel (-1: none yet)
     JpegScratch jpeg;              // evam_pp_encode_jpeg: device scratch and the tables' key
+    JdecScratch jdec;              // evam_pp_decode_jpeg: device scratch and pinned staging
     // Device-resident ROI lists. Both buffers are written and read by kernels only, all on the handle's stream, so
     // stream order makes their reuse safe with any number of calls in flight (evam_pp_set_stream orders a new stream
     // behind the old one); they grow by hipFree + hipMalloc, and hipFree waits for the kernels that still use them.
@@ -4334,6 +4349,11 @@ void evam_pp_destroy(evam_pp* h) {
     h->pin.release(b);
     for (void* p : h->jpeg.buf)
         if (p) (void)hipFree(p);  // waits for kernels that still use it
+    for (void* p : h->jdec.buf)
+        if (p) (void)hipFree(p);
+    if (h->jdec.pin_busy) (void)hipEventSynchronize(h->jdec.pin_ev);
+    if (h->jdec.pin) (void)hipHostFree(h->jdec.pin);
+    if (h->jdec.pin_ev) (void)hipEventDestroy(h->jdec.pin_ev);
     if (h->dev_recs) (void)hipFree(h->dev_recs);
     if (h->dev_cnt) (void)hipFree(h->dev_cnt);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
@@ -5331,3 +5351,4 @@ int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, cons
 }  // extern "C"
 
 #include "evam_jpeg_api.h"
+#include "evam_jpeg_dec_api.h"

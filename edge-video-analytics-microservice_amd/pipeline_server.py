@@ -58,6 +58,7 @@ from ._native import PreProcError
 from .preproc import Image
 
 _WIDTH, _HEIGHT = operator.attrgetter("width"), operator.attrgetter("height")
+_ENCODED = (bytes, bytearray, memoryview)  # a source item of these types is one JPEG file
 INFERENCE_ELEMENTS = ("gvadetect", "gvaclassify", "gvaactionrecognitionbin", "gvainference")
 HIP_BACKENDS = ("hip",)
 # backends DL Streamer 2022.1 accepts that only the reference implements
@@ -1481,6 +1482,7 @@ class Pipeline:
         self._out_backlog = collections.deque()  # runner mode: results a full destination queue could not take
         self._out_limit = 1  # held-back results at which the runner stops ingesting / running this stream
         self._export_pp = None    # destination mode "publisher": this pipeline's handle for export_bgr
+        self._decode_pp = None    # JPEG source items: this pipeline's handle for decode_jpeg
         self._encoding = None     # ... and its ("jpeg", level) when the destination asks for encoded frames
         self._export_host = None  # ... and its pinned host buffer for a tick's packed BGR frames
         # logical device: pipeline k of the server runs on devices[(k - 1) mod G] (streams partitioned over GPUs)
@@ -1594,8 +1596,9 @@ class Pipeline:
             frs = map(FR, map(_WIDTH, got), map(_HEIGHT, got), idx, itertools.repeat(uri, n))
             self._pend.extend(zip(idx, got, frs))
         else:
+            dec = self._decode_burst(got)
             for k, item in enumerate(got):
-                img = self._as_image(item)
+                img = dec[k] if k in dec else self._as_image(item)
                 ts = int(item.get("timestamp", 0)) if isinstance(item, dict) else base + k
                 self._pend.append((base + k, img, FR(img.width, img.height, timestamp=ts, source=uri)))
         self.frames += len(got)
@@ -1698,9 +1701,40 @@ class Pipeline:
             raise PreProcError(N.ERR_UNSUPPORTED, f"source type {src.get('type')!r}: decode is upstream of this "
                                                   "build; use an 'application' source of decoded frames")
 
+    @staticmethod
+    def _jpeg_of(item):
+        """The JPEG file a source item holds (``bytes`` / ``bytearray`` / ``memoryview``, or ``{"jpeg": <those>,
+        "timestamp": t}``: the blobs the reference's subscriber wraps into GstBuffers for ``decodebin``), else None."""
+        if isinstance(item, _ENCODED):
+            return item
+        if isinstance(item, dict) and isinstance(item.get("jpeg"), _ENCODED):
+            return item["jpeg"]
+        return None
+
+    def _new_decoder(self):
+        from . import preproc
+
+        return preproc.HipPreProcessor(device=self.device)
+
+    def _decode_burst(self, got) -> dict:
+        """``{index in got: BGRX Image}`` of every encoded item of one pull: all of them are decoded by one
+        ``decode_jpeg`` (one launch sequence per geometry group) on a decoder handle this pipeline owns, and from there
+        on they are ordinary device frames. ``decode_jpeg`` reads the files' statuses back once, which is one stream
+        synchronisation per pull: a synchronous copy accepted for encoded sources, as the publisher mode's is. A refused
+        or damaged file raises the decoder's ``PreProcError``, which ends the pipeline as every source error does."""
+        at = [k for k, item in enumerate(got) if self._jpeg_of(item) is not None]
+        if not at:
+            return {}
+        if self._decode_pp is None:
+            self._decode_pp = self._new_decoder()
+        imgs = self._decode_pp.decode_jpeg([self._jpeg_of(got[k]) for k in at], "BGRX")
+        return dict(zip(at, imgs))
+
     def _as_image(self, item):
         if isinstance(item, Image):
             return item
+        if self._jpeg_of(item) is not None:
+            return self._decode_burst([item])[0]
         if isinstance(item, dict):         # host frame {fourcc, width, height, planes}
             return Image.from_host(item["fourcc"], item["width"], item["height"], item["planes"],
                                    device=f"cuda:{self.device}")
@@ -1711,6 +1745,9 @@ class Pipeline:
             self._export_pp.close()
             self._export_pp = None
         self._export_host = None
+        if self._decode_pp is not None:
+            self._decode_pp.close()
+            self._decode_pp = None
 
     def _emit(self, fr: P.FrameResult, img, frame=None):
         """One result to the destination: ``(img, fr)`` (mode ``"frames"``), the EVAM publisher's ``(meta, frame

@@ -735,6 +735,86 @@ class HipPreProcessor:
         return files
 
 
+    # -- JPEG decoding of source frames ----------------------------------------------------------------
+    def decode_jpeg_into(self, files, images, status):
+        """Decode ``files`` (bytes-like JPEG files of one geometry: size, components, sampling and restart interval, as
+        :func:`jpeg_info` reports them) into ``images`` (device ``Image``s of that size, all BGR or all BGRX);
+        ``status`` (int32 ``[n]``, device) receives 0 per file, or ``N.ERR_INVALID_ARG`` for a file whose scan is
+        damaged. The bytes are staged before the call returns. Asynchronous, as :meth:`convert`."""
+        torch = self._torch
+        keep, ptrs, lens = N.jpeg_file_arrays(files)
+        n = len(keep)
+        batch = images if isinstance(images, ImageBatch) else ImageBatch(images)
+        if n == 0 or len(batch) != n:
+            raise PreProcError(N.ERR_INVALID_ARG, f"decode_jpeg_into: {n} files for {len(batch)} images")
+        if status.dtype != torch.int32 or status.dim() != 1 or status.shape[0] < n or not status.is_contiguous():
+            raise PreProcError(N.ERR_INVALID_ARG, f"decode_jpeg_into: status must be a contiguous int32 [>= {n}] tensor, "
+                                                  f"got {status.dtype} {tuple(status.shape)}")
+        self._check_device(status)
+        self._bind_stream()
+        rc = self._lib.evam_pp_decode_jpeg(self._h, ptrs, lens, n, batch.c_array, ctypes.c_void_p(status.data_ptr()))
+        if rc:
+            N.check(self._lib, rc)
+
+    def decode_jpeg(self, files, fourcc: int | str = "BGRX") -> list:
+        """Decode JPEG files (bytes-like, any mix of geometries) to device ``Image``s of ``fourcc`` (BGRX or BGR), in
+        the order given: one ``evam_pp_decode_jpeg`` per geometry group, then one read-back of all statuses (one stream
+        synchronisation per call). Raises :class:`PreProcError` naming the first refused or damaged file."""
+        files = list(files)
+        if not files:
+            return []
+        fc = FOURCC_BY_NAME[fourcc] if isinstance(fourcc, str) else int(fourcc)
+        groups: dict = {}
+        for i, f in enumerate(files):
+            try:
+                info = N.jpeg_info_struct(f)
+            except PreProcError as e:
+                raise PreProcError(e.status, f"decode_jpeg: files[{i}]: {e}") from None
+            key = (info.width, info.height, info.components, info.h_samp, info.v_samp, info.restart_interval)
+            groups.setdefault(key, []).append(i)
+        torch = self._torch  # the refusals above need no device
+        dev = f"cuda:{self.device}"
+        status = torch.empty((len(files),), dtype=torch.int32, device=dev)
+        images: list = [None] * len(files)
+        order: list = []
+        at = 0
+        for key, members in groups.items():
+            imgs = [Image.alloc(fc, key[0], key[1], device=dev) for _ in members]
+            self.decode_jpeg_into([files[i] for i in members], imgs, status[at:at + len(members)])
+            for i, im in zip(members, imgs):
+                images[i] = im
+            order += members
+            at += len(members)
+        if not self._follow_torch_stream:  # a stream given at construction: the copy below runs on torch's
+            self.sync()
+        st = status.cpu().tolist()
+        bad = sorted(order[k] for k, v in enumerate(st) if v != 0)
+        if bad:
+            raise PreProcError(N.ERR_INVALID_ARG, f"decode_jpeg: files[{bad[0]}]: the scan is not a valid baseline scan "
+                                                  f"({len(bad)} of {len(files)} files damaged)")
+        return images
+
+
+@dataclass(frozen=True)
+class JpegInfo:
+    """``evam_jpeg_info``: what the markers of a JPEG file up to SOS say."""
+
+    width: int
+    height: int
+    components: int
+    h_samp: int
+    v_samp: int
+    restart_interval: int
+    scan_offset: int
+
+
+def jpeg_info(file) -> JpegInfo:
+    """Parse a JPEG file's header (host only). Raises :class:`PreProcError` (``ERR_UNSUPPORTED`` / ``ERR_INVALID_ARG``
+    with the reason) for a file the decoder refuses."""
+    i = N.jpeg_info_struct(file)
+    return JpegInfo(i.width, i.height, i.components, i.h_samp, i.v_samp, i.restart_interval, i.scan_offset)
+
+
 # Backend registry keyed by the DL Streamer element property value `pre-process-backend`.
 _BACKENDS = {"hip": HipPreProcessor}
 REFERENCE_ONLY_BACKENDS = ("opencv", "ie", "vaapi", "vaapi-surface-sharing")

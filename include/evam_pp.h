@@ -169,7 +169,8 @@ typedef struct evam_pp_stats {
 enum evam_kernel_family {
     EVAM_KERNEL_GENERIC = 1, EVAM_KERNEL_ROWS = 2, EVAM_KERNEL_STAGED = 4, EVAM_KERNEL_WAVE = 8,
     EVAM_KERNEL_STRIP = 16, EVAM_KERNEL_BAND = 32, EVAM_KERNEL_ROI = 64,
-    EVAM_KERNEL_JPEG = 128 /* evam_pp_encode_jpeg: set beside the bits of the export that staged the BGR frame */
+    EVAM_KERNEL_JPEG = 128, /* evam_pp_encode_jpeg: set beside the bits of the export that staged the BGR frame */
+    EVAM_KERNEL_JPEG_DEC = 256 /* evam_pp_decode_jpeg: the only bit after a decode call */
 };
 
 enum evam_pp_option {
@@ -300,6 +301,58 @@ int evam_pp_ssd_rois_host(const float* det, int n_items, int k, const evam_image
  * evam_pp_stats.kernels reports EVAM_KERNEL_ROI; n_items is cap; src_bytes is 0 (the rects are unknown to the host). */
 int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi_list* list,
                             const evam_preproc* cfg, const evam_tensor* dst, int32_t* status);
+
+/* ---- JPEG decoding of source frames (the reference's `{auto_source} ! decodebin` on the cv2.imencode('.jpg') blobs
+ * of its message bus, evas/subscriber.py:92-106, pipelines/object_detection/app_src_dst/pipeline.json:3). Added
+ * without a struct change, so the ABI version stays 3; a library built before them lacks the symbols.
+ *
+ * The pixels are libjpeg's default decode (what cv2.imdecode and jpegdec run): JDCT_ISLOW, fancy up-sampling,
+ * integer YCbCr -> RGB, byte for byte. Served: baseline sequential DCT (SOF0), 8-bit samples, one interleaved scan,
+ * 1 component or 3 with luma sampling (1,1), (2,1) or (2,2) and chroma (1,1), 8-bit DQT, up to two DC and two AC
+ * Huffman tables taken from the file, DRI / RSTn, APPn and COM skipped, JFIF and Adobe (transform 1) files, width and
+ * height 1..32768, files below 2^28 bytes.
+ * The header parse refuses with EVAM_PP_ERR_UNSUPPORTED (nothing launched): SOF1/2/3/5.. (extended, progressive,
+ * lossless, arithmetic), 12-bit samples, 2 or 4 components, any other sampling, 16-bit DQT, more than one scan, a scan
+ * with spectral selection other than 0..63 or a successive-approximation byte other than 0, Adobe transform != 1 with
+ * 3 components. EVAM_PP_ERR_INVALID_ARG: no SOI, a segment length that runs past len, a scan that names a table the
+ * file never defined, a zero size. */
+typedef struct evam_jpeg_info {
+    int32_t width, height;
+    int32_t components;        /* 1 (grey) or 3 (YCbCr) */
+    int32_t h_samp, v_samp;    /* luma sampling factors: (1,1), (2,1) or (2,2); chroma is (1,1) */
+    int32_t restart_interval;  /* MCUs, 0 = none */
+    uint32_t scan_offset;      /* first byte of entropy-coded data */
+} evam_jpeg_info;
+
+/* Parse the markers up to and including SOS. Host-only helper. */
+int evam_pp_jpeg_info(const uint8_t* file, size_t len, evam_jpeg_info* out);
+
+/* Decode n files of one geometry (HOST bytes; width, height, components, sampling and restart interval shared) into
+ * out[i] (HOST descriptors, DEVICE planes, fourcc BGR or BGRX, one fourcc per call; BGRX writes X = 255). Row padding
+ * beyond width x bytes per pixel is never written. status: device int32[n]; status[i] is 0, or EVAM_PP_ERR_INVALID_ARG
+ * for a scan that is no valid baseline scan (a bit pattern that is no code of the active table, a DC category above
+ * 11 or an AC size above 10, a run past coefficient 63, a DC sum that leaves int16, data that ends before the last
+ * MCU, an RSTn out of sequence or missing). The pixels of such a file are unspecified, but every byte written for it
+ * lies inside its own out[i] rows; for any byte sequence every loop of the decoder ends and every access is in bounds.
+ * EVAM_PP_ERR_INVALID_ARG besides the parse's: files that differ in geometry, out[i] of another size, of a fourcc
+ * other than BGR / BGRX, or with a plane pointer or pitch that is no multiple of 16, n outside 1..65535, a NULL
+ * pointer, an out[i] whose pitch x height reaches 2 GiB (a limit of this build, below the 4 GiB of a 32768 x 32768
+ * BGRX frame: larger outputs are untested and refused), files of one call that hold 4 GiB or more together.
+ * The file bytes are copied into pinned staging of the handle before the call returns (the caller may free
+ * them) and from there to device scratch, which grows on demand and is reused (EVAM_PP_ERR_OOM when it cannot).
+ * Asynchronous on the handle's stream, with one limit: a handle owns ONE staging buffer, so a call first waits (on
+ * the host) until the previous decode call's upload has left the staging. That upload is queued on the stream behind
+ * the kernels of the call before it, so on a busy stream at most one decode call runs while the next is staged: the
+ * host is not free to queue many calls ahead. Growing a scratch buffer also waits for the work that uses it.
+ * Callers that must queue several decode calls without a host wait use one handle per call in flight.
+ * evam_pp_stats.kernels reports EVAM_KERNEL_JPEG_DEC. */
+int evam_pp_decode_jpeg(evam_pp* h, const uint8_t* const* files, const size_t* lens, int n,
+                        const evam_image* out, int32_t* status);
+
+/* evam_pp_decode_jpeg on HOST memory only (out planes and status are host pointers): the same shared arithmetic,
+ * driven sequentially, for tests and for callers without a device. Host-only helper. */
+int evam_pp_decode_jpeg_host(const uint8_t* const* files, const size_t* lens, int n,
+                             const evam_image* out, int32_t* status);
 
 #ifdef __cplusplus
 }
