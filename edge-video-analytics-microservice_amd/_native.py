@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "evam_pp_jpeg_header", "evam_pp_encode_jpeg",
     "evam_pp_ssd_rois", "evam_pp_ssd_rois_host", "evam_pp_run_device_rois",
     "evam_pp_jpeg_info", "evam_pp_decode_jpeg", "evam_pp_decode_jpeg_host",
+    "evam_pp_decode_jpeg_planes", "evam_pp_decode_jpeg_planes_host",
 )
 # ... and the one that returns size_t (tests/test_abi.py reads the header's int / void / const char* declarations)
 EXPORTED_SYMBOLS_SIZE_T = ("evam_pp_jpeg_bound",)
@@ -179,6 +180,12 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_decode_jpeg.restype = ctypes.c_int
     lib.evam_pp_decode_jpeg_host.argtypes = dec
     lib.evam_pp_decode_jpeg_host.restype = ctypes.c_int
+    if not hasattr(lib, "evam_pp_decode_jpeg_planes"):  # an A/B variant built before the raw-plane output
+        return lib
+    lib.evam_pp_decode_jpeg_planes.argtypes = [vp] + dec
+    lib.evam_pp_decode_jpeg_planes.restype = ctypes.c_int
+    lib.evam_pp_decode_jpeg_planes_host.argtypes = dec
+    lib.evam_pp_decode_jpeg_planes_host.restype = ctypes.c_int
     return lib
 
 
@@ -282,6 +289,44 @@ def decode_jpeg_host(files, fourcc: int = FOURCC_BGRX, pad: int = 0):
     status = np.full(max(n, 1), 0x7FFFFFFF, np.int32)
     check(lib, lib.evam_pp_decode_jpeg_host(ptrs, lens, n, imgs, status.ctypes.data))
     return buf, pitch, status[:n]
+
+
+def jpeg_planes_ok(info) -> bool:
+    """True when ``evam_pp_decode_jpeg_planes`` serves a file of this header (a ``jpeg_info`` result or the ctypes
+    struct): three components, luma sampling (2,2), even width and height. Any other file decodes to BGR / BGRX."""
+    return (info.components == 3 and info.h_samp == 2 and info.v_samp == 2 and info.width % 2 == 0
+            and info.height % 2 == 0)
+
+
+def decode_jpeg_planes_host(files, fourcc: int = FOURCC_NV12):
+    """``evam_pp_decode_jpeg_planes_host``: the raw planes of 4:2:0 files of one geometry, decoded on the host.
+
+    Returns ``([per file: list of compact uint8 planes], int32 [n] status)``: NV12 ``[Y [H, W], UV [H/2, W]]``, I420
+    ``[Y [H, W], U [H/2, W/2], V [H/2, W/2]]``. Host-only."""
+    import numpy as np
+
+    lib = load_library()
+    keep, ptrs, lens = jpeg_file_arrays(files)
+    n = len(keep)
+    info = jpeg_info_struct(keep[0]) if n else EvamJpegInfo()
+    w, h = info.width, info.height
+    dims = [(h, w), (h // 2, w)] if fourcc == FOURCC_NV12 else [(h, w), (h // 2, w // 2), (h // 2, w // 2)]
+    imgs = (EvamImage * max(n, 1))()
+    bufs = []
+    for i in range(n):
+        imgs[i].fourcc, imgs[i].width, imgs[i].height = fourcc, w, h
+        bufs.append([])
+        for p, (rows, row) in enumerate(dims):
+            pitch = (row + 15) // 16 * 16
+            raw = np.zeros(max(rows, 1) * max(pitch, 16) + 16, np.uint8)
+            off = (-raw.ctypes.data) % 16
+            bufs[i].append(raw[off:off + rows * pitch].reshape(rows, pitch))
+            imgs[i].pitch[p] = pitch
+            imgs[i].planes[p] = raw.ctypes.data + off
+    status = np.full(max(n, 1), 0x7FFFFFFF, np.int32)
+    check(lib, lib.evam_pp_decode_jpeg_planes_host(ptrs, lens, n, imgs, status.ctypes.data))
+    planes = [[np.ascontiguousarray(b[:, :row]) for b, (_, row) in zip(bufs[i], dims)] for i in range(n)]
+    return planes, status[:n]
 
 
 def transforms_array(transforms, n: int):

@@ -526,7 +526,9 @@ EVAM_HD inline uint32_t jdec_pixel(const JdecGeom& g, const uint8_t* planes, int
 // The whole decode of one file on the host, driven sequentially (evam_pp_decode_jpeg_host). The file was parsed.
 // work: g.n_blk * 64 int16 + plane_bytes + scan_len + kJdecStreamPad bytes + (n_int + 1) uint32, carved by the caller.
 // ---------------------------------------------------------------------------------------------------------------
-inline void jdec_dc_and_idct_host(const JdecGeom& g, const JdecFile& file, int16_t* coef, uint8_t* planes, int& err) {
+
+// DC differences -> DC values, per component and restart interval, in place.
+inline void jdec_dc_host(const JdecGeom& g, int16_t* coef, int& err) {
     for (int k = 0; k < g.n_int; k++) {
         int64_t dc[3] = {0, 0, 0};  // 64 bits: a damaged file's sum leaves int32 as well, and only err records it
         const int m0 = g.ri > 0 ? k * g.ri : 0, m1 = g.ri > 0 ? (m0 + g.ri < g.n_mcu ? m0 + g.ri : g.n_mcu) : g.n_mcu;
@@ -537,6 +539,10 @@ inline void jdec_dc_and_idct_host(const JdecGeom& g, const JdecFile& file, int16
             coef[(size_t)blk * 64] = (int16_t)dc[comp];
         }
     }
+}
+
+inline void jdec_dc_and_idct_host(const JdecGeom& g, const JdecFile& file, int16_t* coef, uint8_t* planes, int& err) {
+    jdec_dc_host(g, coef, err);
     for (uint32_t blk = 0; blk < (uint32_t)g.n_blk; blk++) {
         int comp, x0, y0;
         jdec_block_pos(g, blk, comp, x0, y0);
@@ -556,4 +562,85 @@ inline void jdec_colour_host(const JdecGeom& g, const uint8_t* planes, uint8_t* 
             o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
             if (bpp == 4) o[3] = 255;
         }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Raw 4:2:0 planes (evam_pp_decode_jpeg_planes): every component's IDCT output, cropped, straight into the caller's
+// NV12 / I420 planes. No up-sampling and no colour conversion: what libjpeg's jpeg_read_raw_data returns.
+// ---------------------------------------------------------------------------------------------------------------
+
+// One file's output planes (NV12: p[0..1], I420: p[0..2]); bases and pitches are multiples of 16.
+struct JdecPlanesOut {
+    uint8_t* p[3];
+    int32_t pitch[3];
+    int32_t pad[3];
+};
+
+// Geometry the planes path serves: 4:2:0 of even width and height.
+EVAM_HD inline bool jdec_planes_ok(const evam_jpeg_info& in) {
+    return in.components == 3 && in.h_samp == 2 && in.v_samp == 2 && !(in.width & 1) && !(in.height & 1);
+}
+
+// The one store of the planes path: N (8 or 16) bytes px of row y, from byte xb of the row, clipped to a plane of
+// row_bytes x rows pixel bytes. xb is a multiple of N and the plane's base and pitch are multiples of 16, so a
+// segment wholly inside the row is one aligned N-byte store; a segment that straddles the row's end is stored byte by
+// byte up to it; a segment behind it, or a row at or past rows, stores nothing.
+template <int N>
+EVAM_HD inline void jdec_store_clipped(uint8_t* plane, int pitch, int xb, int y, int row_bytes, int rows,
+                                       const uint8_t* px) {
+    static_assert(N == 8 || N == 16, "an 8- or 16-byte segment");
+    typedef uint32_t Seg __attribute__((vector_size(N), may_alias));  // one store instruction, aligned to N
+    if (y >= rows || xb >= row_bytes) return;
+    uint8_t* o = plane + (size_t)y * pitch + xb;
+    if (xb + N <= row_bytes) {
+        Seg v;
+        memcpy(&v, px, N);
+        *reinterpret_cast<Seg*>(o) = v;
+    } else {
+        for (int i = 0; xb + i < row_bytes; i++) o[i] = px[i];
+    }
+}
+
+constexpr int kJdecPlaneRows = 24;  // row tasks of one 4:2:0 MCU: 16 luma rows, 8 chroma rows
+
+// Row task t of MCU `mcu` from the column pass's six workspaces ws[6][64] (Y00 Y01 Y10 Y11 Cb Cr, the scan's order).
+// t < 16: luma row t of the MCU, the rows of its two horizontally adjacent blocks as one 16-byte segment.
+// t >= 16: row t - 16 of the Cb and the Cr block: 16 interleaved bytes (NV12) or 8 bytes into each plane (I420).
+template <bool NV12>
+EVAM_HD inline void jdec_planes_row(const JdecGeom& g, const JdecPlanesOut& o, int mcu, int t, const int32_t* ws) {
+    const int mxi = mcu % g.mx, myi = mcu / g.mx;
+    alignas(16) uint8_t px[16];
+    if (t < 16) {
+        const int32_t* w = ws + (t >> 3) * 128;
+        jdec_idct_row(w, t & 7, px);
+        jdec_idct_row(w + 64, t & 7, px + 8);
+        jdec_store_clipped<16>(o.p[0], o.pitch[0], mxi * 16, myi * 16 + t, g.W, g.H, px);
+        return;
+    }
+    const int r = t - 16, y = myi * 8 + r;
+    if (NV12) {
+        uint8_t cb[8], cr[8];
+        jdec_idct_row(ws + 4 * 64, r, cb);
+        jdec_idct_row(ws + 5 * 64, r, cr);
+        for (int i = 0; i < 8; i++) { px[2 * i] = cb[i]; px[2 * i + 1] = cr[i]; }
+        jdec_store_clipped<16>(o.p[1], o.pitch[1], mxi * 16, y, g.W, g.H / 2, px);
+    } else {
+        jdec_idct_row(ws + 4 * 64, r, px);
+        jdec_idct_row(ws + 5 * 64, r, px + 8);
+        jdec_store_clipped<8>(o.p[1], o.pitch[1], mxi * 8, y, g.W / 2, g.H / 2, px);
+        jdec_store_clipped<8>(o.p[2], o.pitch[2], mxi * 8, y, g.W / 2, g.H / 2, px + 8);
+    }
+}
+
+// The host twin of evam_jdec_idct_planes: the same row tasks, MCU by MCU. coef holds the scan's raw DC differences.
+template <bool NV12>
+inline void jdec_planes_host(const JdecGeom& g, const JdecFile& file, int16_t* coef, const JdecPlanesOut& o, int& err) {
+    jdec_dc_host(g, coef, err);
+    int32_t ws[6 * 64];
+    for (int mcu = 0; mcu < g.n_mcu; mcu++) {
+        for (int k = 0; k < 6; k++)
+            for (int c = 0; c < 8; c++)
+                jdec_idct_column(coef + ((size_t)mcu * 6 + k) * 64, file.q[k < 4 ? 0 : k - 3], c, ws + k * 64);
+        for (int t = 0; t < kJdecPlaneRows; t++) jdec_planes_row<NV12>(g, o, mcu, t, ws);
+    }
 }

@@ -9,6 +9,7 @@
 //   4 evam_jdec_dc       one workgroup per (interval, file): DC differences -> DC values, per component
 //   5 evam_jdec_idct     eight threads per block: dequantise, both IDCT passes, range limit -> component planes
 //   6 evam_jdec_colour   one thread per VEC pixels: fancy up-sampling + YCbCr -> BGR / BGRX rows
+// evam_pp_decode_jpeg_planes runs kernels 1 to 4 and then evam_jdec_idct_planes in place of 5 and 6: five launches.
 //
 // No kernel talks to another workgroup: every hand-off is a kernel boundary on the handle's stream. Every loop over
 // file data is bounded by a length the host validated (scan_len, n_int, n_slots, n_mcu) and every store is checked
@@ -24,7 +25,8 @@ struct JdecOut {
 struct JdecParams {
     JdecGeom g;
     const JdecFile* files;   // [n]
-    const JdecOut* outs;     // [n]
+    const JdecOut* outs;     // [n] (BGR / BGRX output)
+    const JdecPlanesOut* pouts;  // [n] (NV12 / I420 output)
     const uint8_t* raw;      // the files' entropy-coded bytes, file i at files[i].raw_off
     uint8_t* stream;         // [n][stream_stride] compacted scans
     uint32_t stream_stride;
@@ -32,7 +34,7 @@ struct JdecParams {
     uint4* slots;            // [n][n_slots] sub-sequence records: entry p, entry bz, first block, interval + 1
     uint32_t n_slots;
     int16_t* coef;           // [n][n_blk][64], zig-zag order
-    uint8_t* planes;         // [n][plane_bytes]
+    uint8_t* planes;         // [n][plane_bytes] (BGR / BGRX output only)
     int32_t* status;         // [n]
 };
 
@@ -277,6 +279,29 @@ __global__ __launch_bounds__(256) void evam_jdec_idct(const JdecParams P) {
     const int pitch = comp == 0 ? P.g.yp : P.g.cp;
     uint8_t* o = P.planes + (size_t)fi * P.g.plane_bytes + jdec_plane_off(P.g, comp) + (size_t)(y0 + c) * pitch + x0;
     *reinterpret_cast<uint2*>(o) = px.v;  // 8-byte aligned: x0, the pitches and the plane offsets are multiples of 8
+}
+
+// The planes path's kernel 5 (evam_pp_decode_jpeg_planes, 4:2:0 only): coefficients -> the caller's NV12 / I420 planes,
+// with no component planes in scratch and no second pass. A workgroup takes kJdecPlaneMcus MCUs: eight threads per
+// block run the column pass into LDS, then kJdecPlaneRows threads per MCU each finish two block rows and store them
+// as one 16-byte segment (I420 chroma: two 8-byte segments), clipped by jdec_store_clipped.
+constexpr int kJdecPlaneMcus = 5;  // 30 blocks: 240 of 256 threads in the column pass, 120 in the row pass
+
+template <bool NV12>
+__global__ __launch_bounds__(256) void evam_jdec_idct_planes(const JdecParams P) {
+    __shared__ int32_t s_ws[kJdecPlaneMcus * 6][64];
+    const int tid = threadIdx.x, fi = blockIdx.y;
+    const uint32_t mcu0 = blockIdx.x * (uint32_t)kJdecPlaneMcus;
+    const int lb = tid >> 3, c = tid & 7;
+    const uint32_t blk = mcu0 * 6u + lb;
+    if (lb < kJdecPlaneMcus * 6 && blk < (uint32_t)P.g.n_blk) {
+        const int k = lb % 6;
+        jdec_idct_column(P.coef + ((size_t)fi * P.g.n_blk + blk) * 64, P.files[fi].q[k < 4 ? 0 : k - 3], c, s_ws[lb]);
+    }
+    __syncthreads();
+    const int lm = tid / kJdecPlaneRows, t = tid % kJdecPlaneRows;
+    if (lm >= kJdecPlaneMcus || mcu0 + lm >= (uint32_t)P.g.n_mcu) return;
+    jdec_planes_row<NV12>(P.g, P.pouts[fi], (int)(mcu0 + lm), t, s_ws[lm * 6]);
 }
 
 // VEC pixels per thread; VEC * BPP bytes are stored as 32-bit words (one 16-byte store for 4 BGRX pixels), the row's

@@ -1450,8 +1450,25 @@ def publisher_encoding(destination):
     return kind, level
 
 
+JPEG_FORMATS = ("BGRX", "I420", "NV12")
+
+
+def source_jpeg_format(source) -> str:
+    """The ``"jpeg_format"`` of an ``application`` / ``frames`` source: what its JPEG items are decoded to. ``"BGRX"``
+    (the default) is libjpeg's default decode; ``"I420"`` / ``"NV12"`` are the files' raw 4:2:0 planes, the frames the
+    reference's ``jpegdec`` hands ``gvadetect`` (files without such planes still come as BGRX). Any other value is
+    ``ERR_INVALID_ARG``, refused when the pipeline starts."""
+    fmt = (source or {}).get("jpeg_format", "BGRX")
+    if not isinstance(fmt, str) or fmt not in JPEG_FORMATS:
+        raise N.PreProcError(N.ERR_INVALID_ARG, f"source \"jpeg_format\" must be one of {', '.join(JPEG_FORMATS)}, "
+                                                f"got {fmt!r}")
+    return fmt
+
+
 class Pipeline:
     """One pipeline instance (``PipelineServer.pipeline(name, version)``)."""
+
+    _jpeg_format = "BGRX"  # JPEG source items are decoded to this (source option "jpeg_format")
 
     QUEUED, RUNNING, COMPLETED, ERROR, ABORTED = "QUEUED", "RUNNING", "COMPLETED", "ERROR", "ABORTED"
     kIngest = 1024  # device runner: most frames of one stream ingested and not yet run
@@ -1516,6 +1533,7 @@ class Pipeline:
     def start(self, source=None, destination=None, parameters=None):
         """Build the element graph, instantiate the HIP stages, and run the frame loop in a thread."""
         self._encoding = publisher_encoding(destination)  # refused here, before anything runs
+        self._jpeg_format = source_jpeg_format(source)    # likewise
         self.build(source, parameters)
         self.stages = [STAGES[e.factory](e, self.server, self.device, self.slot)
                        for e in self.elements if e.factory in STAGES]
@@ -1717,17 +1735,23 @@ class Pipeline:
         return preproc.HipPreProcessor(device=self.device)
 
     def _decode_burst(self, got) -> dict:
-        """``{index in got: BGRX Image}`` of every encoded item of one pull: all of them are decoded by one
+        """``{index in got: Image}`` of every encoded item of one pull: all of them are decoded by one
         ``decode_jpeg`` (one launch sequence per geometry group) on a decoder handle this pipeline owns, and from there
         on they are ordinary device frames. ``decode_jpeg`` reads the files' statuses back once, which is one stream
         synchronisation per pull: a synchronous copy accepted for encoded sources, as the publisher mode's is. A refused
-        or damaged file raises the decoder's ``PreProcError``, which ends the pipeline as every source error does."""
+        or damaged file raises the decoder's ``PreProcError``, which ends the pipeline as every source error does.
+        The images are BGRX, or with the source's ``"jpeg_format"`` ``"I420"`` / ``"NV12"`` the files' raw planes, where
+        a file has them (4:2:0, even size), and BGRX otherwise: a stream may mix both."""
         at = [k for k, item in enumerate(got) if self._jpeg_of(item) is not None]
         if not at:
             return {}
         if self._decode_pp is None:
             self._decode_pp = self._new_decoder()
-        imgs = self._decode_pp.decode_jpeg([self._jpeg_of(got[k]) for k in at], "BGRX")
+        files = [self._jpeg_of(got[k]) for k in at]
+        if self._jpeg_format == "BGRX":
+            imgs = self._decode_pp.decode_jpeg(files, "BGRX")
+        else:
+            imgs = self._decode_pp.decode_jpeg(files, self._jpeg_format, fallback="BGRX")
         return dict(zip(at, imgs))
 
     def _as_image(self, item):

@@ -738,7 +738,9 @@ class HipPreProcessor:
     # -- JPEG decoding of source frames ----------------------------------------------------------------
     def decode_jpeg_into(self, files, images, status):
         """Decode ``files`` (bytes-like JPEG files of one geometry: size, components, sampling and restart interval, as
-        :func:`jpeg_info` reports them) into ``images`` (device ``Image``s of that size, all BGR or all BGRX);
+        :func:`jpeg_info` reports them) into ``images`` (device ``Image``s of that size, all of one fourcc). BGR / BGRX
+        images receive libjpeg's default decode (``evam_pp_decode_jpeg``); NV12 / I420 images receive the files' raw
+        4:2:0 planes (``evam_pp_decode_jpeg_planes``: 4:2:0 files of even size only, see :func:`jpeg_planes_ok`).
         ``status`` (int32 ``[n]``, device) receives 0 per file, or ``N.ERR_INVALID_ARG`` for a file whose scan is
         damaged. The bytes are staged before the call returns. Asynchronous, as :meth:`convert`."""
         torch = self._torch
@@ -752,18 +754,30 @@ class HipPreProcessor:
                                                   f"got {status.dtype} {tuple(status.shape)}")
         self._check_device(status)
         self._bind_stream()
-        rc = self._lib.evam_pp_decode_jpeg(self._h, ptrs, lens, n, batch.c_array, ctypes.c_void_p(status.data_ptr()))
+        planes = batch.images[0].fourcc in (N.FOURCC_NV12, N.FOURCC_I420)
+        call = self._lib.evam_pp_decode_jpeg_planes if planes else self._lib.evam_pp_decode_jpeg
+        rc = call(self._h, ptrs, lens, n, batch.c_array, ctypes.c_void_p(status.data_ptr()))
         if rc:
             N.check(self._lib, rc)
 
-    def decode_jpeg(self, files, fourcc: int | str = "BGRX") -> list:
-        """Decode JPEG files (bytes-like, any mix of geometries) to device ``Image``s of ``fourcc`` (BGRX or BGR), in
-        the order given: one ``evam_pp_decode_jpeg`` per geometry group, then one read-back of all statuses (one stream
-        synchronisation per call). Raises :class:`PreProcError` naming the first refused or damaged file."""
+    def decode_jpeg(self, files, fourcc: int | str = "BGRX", fallback: int | str | None = None) -> list:
+        """Decode JPEG files (bytes-like, any mix of geometries) to device ``Image``s of ``fourcc``, in the order
+        given: one decode call per geometry group, then one read-back of all statuses (one stream synchronisation per
+        call). ``fourcc`` BGRX or BGR is libjpeg's default decode; NV12 or I420 is the files' raw 4:2:0 planes, which
+        only files that :func:`jpeg_planes_ok` accepts have: any other file raises ``ERR_UNSUPPORTED``, or with
+        ``fallback`` ("BGRX" / "BGR") comes back decoded to that format instead. Raises :class:`PreProcError` naming
+        the first refused or damaged file."""
         files = list(files)
         if not files:
             return []
         fc = FOURCC_BY_NAME[fourcc] if isinstance(fourcc, str) else int(fourcc)
+        planes = fc in (N.FOURCC_NV12, N.FOURCC_I420)
+        fb = None
+        if fallback is not None:
+            fb = FOURCC_BY_NAME.get(fallback) if isinstance(fallback, str) else int(fallback)
+            if not planes or fb not in (N.FOURCC_BGRX, N.FOURCC_BGR):
+                raise PreProcError(N.ERR_INVALID_ARG, f"decode_jpeg: fallback {fallback!r}: \"BGRX\" or \"BGR\", beside "
+                                                      "an NV12 / I420 fourcc")
         groups: dict = {}
         for i, f in enumerate(files):
             try:
@@ -771,6 +785,16 @@ class HipPreProcessor:
             except PreProcError as e:
                 raise PreProcError(e.status, f"decode_jpeg: files[{i}]: {e}") from None
             key = (info.width, info.height, info.components, info.h_samp, info.v_samp, info.restart_interval)
+            if planes:
+                if N.jpeg_planes_ok(info):
+                    key += (fc,)
+                elif fb is None:
+                    raise PreProcError(N.ERR_UNSUPPORTED, f"decode_jpeg: files[{i}]: {info.width}x{info.height}, "
+                                       f"{info.components} components, luma sampling {info.h_samp}x{info.v_samp}: raw "
+                                       f"{NAME_BY_FOURCC[fc]} planes are written for 4:2:0 files of even size only "
+                                       "(pass fallback=\"BGRX\" to decode such files to pixels)")
+                else:
+                    key += (fb,)
             groups.setdefault(key, []).append(i)
         torch = self._torch  # the refusals above need no device
         dev = f"cuda:{self.device}"
@@ -779,7 +803,7 @@ class HipPreProcessor:
         order: list = []
         at = 0
         for key, members in groups.items():
-            imgs = [Image.alloc(fc, key[0], key[1], device=dev) for _ in members]
+            imgs = [Image.alloc(key[6] if planes else fc, key[0], key[1], device=dev) for _ in members]
             self.decode_jpeg_into([files[i] for i in members], imgs, status[at:at + len(members)])
             for i, im in zip(members, imgs):
                 images[i] = im
@@ -806,6 +830,9 @@ class JpegInfo:
     v_samp: int
     restart_interval: int
     scan_offset: int
+
+
+jpeg_planes_ok = N.jpeg_planes_ok  # re-export: which files decode_jpeg(..., "NV12" / "I420") serves
 
 
 def jpeg_info(file) -> JpegInfo:

@@ -354,6 +354,31 @@ int evam_pp_decode_jpeg(evam_pp* h, const uint8_t* const* files, const size_t* l
 int evam_pp_decode_jpeg_host(const uint8_t* const* files, const size_t* lens, int n,
                              const evam_image* out, int32_t* status);
 
+/* ---- JPEG sources as raw 4:2:0 planes (what the reference's `decodebin` hands gvadetect: jpegdec's I420 planes, which
+ * the pre-processor then converts with the limited-range BT.601 arithmetic of evam_pp_run). Symbols added, no struct
+ * changed: the ABI version stays 3.
+ *
+ * evam_pp_decode_jpeg with out[i] of fourcc NV12 or I420 (one fourcc per call): the planes are what libjpeg's
+ * jpeg_read_raw_data returns, every component's jpeg_idct_islow output after the range limit, with no up-sampling and
+ * no colour conversion. Y is cropped to width x height; Cb is cropped to width/2 x height/2 and becomes U, Cr
+ * likewise V; NV12 interleaves U, V. Each used plane of out[i] (NV12: 0, 1; I420: 0, 1, 2) has its own pointer and
+ * pitch, both multiples of 16, the pitch at least the row bytes, pitch x rows below 2 GiB; planes may lie in any order
+ * and at any distance and may be windows of a larger surface. Only pixel bytes are ever written: width bytes of each
+ * of height luma rows, and width (NV12) or width/2 (I420) bytes of each of height/2 chroma rows. Row padding, the gap
+ * between planes and the surface around a window are never touched, for a damaged file as well.
+ * Served: 3-component files with luma sampling (2,2) and even width and height (what evam_image admits for 4:2:0).
+ * Any other file is refused with EVAM_PP_ERR_UNSUPPORTED before any work ("sampling" / "odd" in the message, which
+ * names files[i]); such a file still decodes to BGR / BGRX with evam_pp_decode_jpeg. Every other refusal, the status
+ * array, restart intervals, damaged scans and the staging are those of evam_pp_decode_jpeg.
+ * evam_pp_stats.kernels reports EVAM_KERNEL_JPEG_DEC; n_launches is 5 (no component planes in scratch and no colour
+ * pass: the IDCT kernel writes the caller's planes). */
+int evam_pp_decode_jpeg_planes(evam_pp* h, const uint8_t* const* files, const size_t* lens, int n,
+                               const evam_image* out, int32_t* status);
+
+/* evam_pp_decode_jpeg_planes on HOST memory only (host planes, host status). Host-only helper. */
+int evam_pp_decode_jpeg_planes_host(const uint8_t* const* files, const size_t* lens, int n,
+                                    const evam_image* out, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,16 +2,19 @@
 """JPEG decoding of source frames, measured (bench.py is the flagship's yardstick and is not involved).
 
   python tools/jpeg_dec_bench.py [--files 32] [--steps 20] [--warmup 3] [--content noise|smooth]
+                                 [--fourcc BGRX|NV12|I420]
 
 The files are 1080p frames of bench.device_frames content, encoded by HipPreProcessor.encode_jpeg at quality 90.
+--fourcc BGRX is libjpeg's default decode (evam_pp_decode_jpeg); NV12 / I420 are the files' raw 4:2:0 planes
+(evam_pp_decode_jpeg_planes: five kernels, no component planes in scratch, no colour pass).
 Measured for --files files per call and for one file alone:
-  - device time per evam_pp_decode_jpeg call and files/s, by HIP events around --steps calls launched back to back
+  - device time per decode call and files/s, by HIP events around --steps calls launched back to back
     (launches in flight, as bench.py runs its steps);
   - host time per call (parse, staging copy, launches), from the wall clock of the launching loop;
   - HipPreProcessor.decode_jpeg (allocation, call, status read-back) per call;
   - the library's own host twin (evam_pp_decode_jpeg_host) on one core;
   - Pillow on 16 threads decoding the same files, where Pillow imports.
-Per-kernel times: run it under `rocprofv3 --kernel-trace --stats --` (the six evam_jdec_* kernels appear by name).
+Per-kernel times: run it under `rocprofv3 --kernel-trace --stats --` (the evam_jdec_* kernels appear by name).
 Prints one JSON line."""
 import argparse
 import io
@@ -38,9 +41,9 @@ def make_files(evam, torch, pp, n, content, dev):
     return pp.encode_jpeg(imgs, 90), imgs[0].width, imgs[0].height
 
 
-def measure(evam, torch, pp, files, w, h, steps, warmup, dev):
+def measure(evam, torch, pp, files, w, h, steps, warmup, dev, fourcc):
     n = len(files)
-    imgs = evam.ImageBatch([evam.Image.alloc("BGRX", w, h, device=dev) for _ in range(n)])
+    imgs = evam.ImageBatch([evam.Image.alloc(fourcc, w, h, device=dev) for _ in range(n)])
     status = torch.zeros(n, dtype=torch.int32, device=dev)
     for _ in range(warmup):
         pp.decode_jpeg_into(files, imgs, status)
@@ -57,7 +60,7 @@ def measure(evam, torch, pp, files, w, h, steps, warmup, dev):
     dev_us = e0.elapsed_time(e1) / steps * 1e3
     t0 = time.perf_counter()
     for _ in range(max(steps // 4, 1)):
-        pp.decode_jpeg(files)
+        pp.decode_jpeg(files, fourcc)
     api_us = (time.perf_counter() - t0) / max(steps // 4, 1) * 1e6
     return {"files": n, "us_per_call": round(dev_us, 1), "files_per_s": round(n / dev_us * 1e6, 1),
             "host_us_per_call": round(host_us, 1), "decode_jpeg_us_per_call": round(api_us, 1)}
@@ -69,6 +72,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--content", choices=("noise", "smooth"), default="smooth")
+    ap.add_argument("--fourcc", choices=("BGRX", "NV12", "I420"), default="BGRX")
     args = ap.parse_args()
     import torch
 
@@ -78,12 +82,15 @@ def main():
     dev = torch.device("cuda:0")
     pp = evam.HipPreProcessor(device=0)
     files, w, h = make_files(evam, torch, pp, args.files, args.content, dev)
-    out = {"what": "jpeg decode", "size": [w, h], "quality": 90, "content": args.content,
+    out = {"what": "jpeg decode", "fourcc": args.fourcc, "size": [w, h], "quality": 90, "content": args.content,
            "file_bytes_mean": int(sum(map(len, files)) / len(files)), "device": torch.cuda.get_device_name(0),
-           "batch": measure(evam, torch, pp, files, w, h, args.steps, args.warmup, dev),
-           "single": measure(evam, torch, pp, files[:1], w, h, args.steps, args.warmup, dev)}
+           "batch": measure(evam, torch, pp, files, w, h, args.steps, args.warmup, dev, args.fourcc),
+           "single": measure(evam, torch, pp, files[:1], w, h, args.steps, args.warmup, dev, args.fourcc)}
     t0 = time.perf_counter()
-    evam.native.decode_jpeg_host(files[:4])
+    if args.fourcc == "BGRX":
+        evam.native.decode_jpeg_host(files[:4])
+    else:
+        evam.native.decode_jpeg_planes_host(files[:4], evam.preproc.FOURCC_BY_NAME[args.fourcc])
     out["host_twin_one_core_files_per_s"] = round(4 / (time.perf_counter() - t0), 2)
     try:
         from PIL import Image
