@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = (
     "evam_pp_ssd_rois", "evam_pp_ssd_rois_host", "evam_pp_run_device_rois",
     "evam_pp_jpeg_info", "evam_pp_decode_jpeg", "evam_pp_decode_jpeg_host",
     "evam_pp_decode_jpeg_planes", "evam_pp_decode_jpeg_planes_host",
+    "evam_pp_track_host", "evam_pp_tracker_create", "evam_pp_tracker_destroy", "evam_pp_tracker_reset",
+    "evam_pp_tracker_read", "evam_pp_track_device_rois", "evam_pp_ssd_rois_ex",
 )
 # ... and the one that returns size_t (tests/test_abi.py reads the header's int / void / const char* declarations)
 EXPORTED_SYMBOLS_SIZE_T = ("evam_pp_jpeg_bound",)
@@ -110,6 +112,28 @@ class EvamJpegInfo(ctypes.Structure):
                 ("restart_interval", c_i32), ("scan_offset", ctypes.c_uint32)]
 
 
+TRACK_SLOTS, TRACK_DETS, TRACK_NONE = 128, 128, 0xFFFFFFFF  # EVAM_TRACK_*
+
+
+class EvamTrackSlot(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_uint32), ("label", c_i32), ("x", c_i32), ("y", c_i32), ("w", c_i32), ("h", c_i32),
+                ("lost", c_i32), ("classified_at", ctypes.c_uint32)]
+
+
+class EvamTrackState(ctypes.Structure):
+    """``evam_track_state``: one stream's tracker state. Zeroed memory counts as a fresh state."""
+
+    _fields_ = [("next_id", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 7), ("slots", EvamTrackSlot * TRACK_SLOTS)]
+
+
+class EvamTrackCfg(ctypes.Structure):
+    _fields_ = [("max_lost", c_i32), ("iou_threshold", ctypes.c_float)]
+
+
+class EvamTrackItem(ctypes.Structure):
+    _fields_ = [("stream", c_i32), ("frame", ctypes.c_uint32)]
+
+
 # evam_pp_stats.kernels bits (include/evam_pp.h evam_kernel_family)
 KERNEL_GENERIC, KERNEL_ROWS, KERNEL_STAGED, KERNEL_WAVE = 1, 2, 4, 8
 KERNEL_STRIP, KERNEL_BAND, KERNEL_ROI = 16, 32, 64
@@ -120,7 +144,8 @@ JPEG_HEADER_LEN = 623  # SOI .. SOS of every file evam_pp_encode_jpeg writes
 
 
 STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32,
-                EvamRoiList: 24, EvamJpegInfo: 28}
+                EvamRoiList: 24, EvamJpegInfo: 28, EvamTrackSlot: 32, EvamTrackState: 4128, EvamTrackCfg: 8,
+                EvamTrackItem: 8}
 
 _LIB = None
 
@@ -186,6 +211,22 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_decode_jpeg_planes.restype = ctypes.c_int
     lib.evam_pp_decode_jpeg_planes_host.argtypes = dec
     lib.evam_pp_decode_jpeg_planes_host.restype = ctypes.c_int
+    lib.evam_pp_track_host.argtypes = [P(EvamTrackState), P(EvamTrackCfg), ctypes.c_uint32, vp, vp, ctypes.c_int,
+                                       vp, ctypes.c_int, ctypes.c_int, vp, vp]
+    lib.evam_pp_track_host.restype = ctypes.c_int
+    lib.evam_pp_tracker_create.argtypes = [vp, ctypes.c_int, P(EvamTrackCfg), P(vp)]
+    lib.evam_pp_tracker_create.restype = ctypes.c_int
+    lib.evam_pp_tracker_destroy.argtypes = [vp]
+    lib.evam_pp_tracker_destroy.restype = None
+    lib.evam_pp_tracker_reset.argtypes = [vp, vp, ctypes.c_int]
+    lib.evam_pp_tracker_reset.restype = ctypes.c_int
+    lib.evam_pp_tracker_read.argtypes = [vp, vp, ctypes.c_int, P(EvamTrackState)]
+    lib.evam_pp_tracker_read.restype = ctypes.c_int
+    lib.evam_pp_track_device_rois.argtypes = [vp, vp, P(EvamRoiList), vp, ctypes.c_int, P(EvamTrackItem), vp,
+                                              ctypes.c_int, ctypes.c_int, vp, P(EvamRoiList)]
+    lib.evam_pp_track_device_rois.restype = ctypes.c_int
+    lib.evam_pp_ssd_rois_ex.argtypes = [vp] + ssd + [vp]
+    lib.evam_pp_ssd_rois_ex.restype = ctypes.c_int
     return lib
 
 
@@ -380,6 +421,79 @@ def ssd_rois_host(det, sizes, transforms, tensor_size, threshold: float, labels=
         None if lab is None else lab.ctypes.data_as(ctypes.POINTER(c_i32)), 0 if lab is None else int(lab.size),
         ctypes.byref(lst)))
     return rois[:min(int(count.value), cap)].copy(), int(count.value)
+
+
+TRACKING_TYPES = {"zero-term-imageless": 0, "short-term-imageless": 8}  # gvatrack tracking-type -> max_lost
+TRACK_IOU_THRESHOLD = 0.3
+
+
+def track_cfg(tracking_type=None, iou_threshold: float = TRACK_IOU_THRESHOLD) -> EvamTrackCfg:
+    """The ``evam_track_cfg`` of a gvatrack element's ``tracking-type`` (absent: ``short-term-imageless``). The types
+    that need image features (``zero-term``, ``short-term``) are ``ERR_UNSUPPORTED``; an unknown one is
+    ``ERR_INVALID_ARG``."""
+    kind = "short-term-imageless" if tracking_type in (None, "") else str(tracking_type)
+    if kind in ("zero-term", "short-term"):
+        raise PreProcError(ERR_UNSUPPORTED, f"tracking-type {kind!r} needs image features, which this tracker does not "
+                                            f"compute; use {' or '.join(sorted(TRACKING_TYPES))}")
+    if kind not in TRACKING_TYPES:
+        raise PreProcError(ERR_INVALID_ARG, f"tracking-type {kind!r} is not one of {', '.join(sorted(TRACKING_TYPES))}")
+    return EvamTrackCfg(TRACKING_TYPES[kind], float(iou_threshold))
+
+
+def classify_set_args(classify_labels):
+    """``(kept array, pointer, n)`` of a gate's label set: None is no gate, ``"all"`` every label, else label ids."""
+    import numpy as np
+
+    if classify_labels is None:
+        return None, None, 0
+    if isinstance(classify_labels, str):
+        if classify_labels != "all":
+            raise PreProcError(ERR_INVALID_ARG, f"classify_labels {classify_labels!r}: None, \"all\" or label ids")
+        return None, None, -1
+    a = np.ascontiguousarray(list(classify_labels), dtype=np.int32)
+    keep = a if a.size else np.zeros(1, np.int32)
+    return keep, ctypes.c_void_p(keep.ctypes.data), int(a.size)
+
+
+class HostTracker:
+    """One stream's tracker on the host (``evam_pp_track_host``): the state lives in this object. Needs no GPU."""
+
+    def __init__(self, tracking_type=None, iou_threshold: float = TRACK_IOU_THRESHOLD, cfg: EvamTrackCfg | None = None):
+        self._lib = load_library()
+        self.cfg = cfg if cfg is not None else track_cfg(tracking_type, iou_threshold)
+        self.state = EvamTrackState()
+
+    def reset(self):
+        self.state = EvamTrackState()
+
+    def step(self, frame: int, boxes, labels, classify_labels=None, reclassify: int = 1):
+        """One frame: ``boxes`` ``[n, 4]`` rows of (x, y, w, h) and ``labels`` ``[n]`` in list order. Returns
+        ``(uint32 [n] ids, bool [n] due)``; ``classify_labels`` as for :func:`classify_set_args`."""
+        import numpy as np
+
+        b = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+        n = len(b)
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if len(lab) != n:
+            raise PreProcError(ERR_INVALID_ARG, f"{len(lab)} labels for {n} boxes")
+        rois = np.zeros((max(n, 1), 5), np.int32)
+        rois[:n, 1:] = b
+        ids = np.zeros(max(n, 1), np.uint32)
+        due = np.zeros(max(n, 1), np.uint8)
+        keep, ptr, n_set = classify_set_args(classify_labels)
+        check(self._lib, self._lib.evam_pp_track_host(
+            ctypes.byref(self.state), ctypes.byref(self.cfg), int(frame), rois.ctypes.data, lab.ctypes.data if n else None,
+            n, ptr, n_set, int(reclassify), ids.ctypes.data, due.ctypes.data))
+        return ids[:n], due[:n].astype(bool)
+
+
+def track_state_tuple(state: EvamTrackState):
+    """``(next_id, [(id, label, x, y, w, h, lost, classified_at) per slot])`` of a state; a zeroed (never used) state
+    reads as the fresh state it stands for."""
+    if state.next_id == 0:
+        return 1, [(0, 0, 0, 0, 0, 0, 0, TRACK_NONE)] * TRACK_SLOTS
+    return int(state.next_id), [(int(s.id), int(s.label), int(s.x), int(s.y), int(s.w), int(s.h), int(s.lost),
+                                 int(s.classified_at)) for s in state.slots]
 
 
 class PreProcError(RuntimeError):

@@ -48,6 +48,7 @@
 #include "evam_rings.h"
 #include "evam_clip_simd.h"
 #include "evam_jpeg_dec.h"
+#include "evam_track.h"
 
 namespace {
 
@@ -3145,9 +3146,10 @@ struct SsdParams {
     uint32_t* count;
     int n_items, k, n_labels, TW, TH, cap;
     float threshold;
+    int32_t* out_labels;       // evam_pp_ssd_rois_ex (LAB): the label of each list entry, [cap]
 };
 
-template <bool EMIT>
+template <bool EMIT, bool LAB = false>
 __global__ __launch_bounds__(kThreads) void evam_pp_ssd_rows(const SsdParams P) {
     __shared__ int s_end;
     __shared__ uint32_t s_w[kThreads / 64];
@@ -3185,6 +3187,10 @@ __global__ __launch_bounds__(kThreads) void evam_pp_ssd_rows(const SsdParams P) 
             if (pos < (uint32_t)P.cap) {
                 int32_t* o = reinterpret_cast<int32_t*>(P.rois + pos);
                 o[0] = i; o[1] = x; o[2] = y; o[3] = w; o[4] = h;
+                if (LAB) {  // int(label), as the host path truncates it
+                    const float lf = d[(size_t)r * 7 + 1];
+                    P.out_labels[pos] = (lf - lf == 0.f) && lf < 2147483648.f && lf >= -2147483648.f ? (int32_t)lf : 0;
+                }
             }
         }
         total += all;
@@ -4177,6 +4183,7 @@ using PinRing = PinRingT<HipRings>;
 
 #include "evam_jpeg_kernels.h"
 #include "evam_jpeg_dec_kernels.h"
+#include "evam_track_kernels.h"
 
 // evam_pp_decode_jpeg: device scratch (grown on demand, reused) and the pinned staging of the file bytes.
 enum { kJdUp = 0, kJdStream, kJdFirst, kJdSlots, kJdCoef, kJdPlanes, kJdCount };
@@ -4252,6 +4259,7 @@ struct evam_pp {
     std::vector<uint8_t> h_aux;    // their host-built block (per-source table / per-item sizes, transforms, labels)
     DescRing ring_ssd;             // evam_pp_ssd_rois' block: a ring of its own, so that a detect -> classify chain that
                                    // alternates it with evam_pp_run_device_rois' block re-uploads neither when unchanged
+    DescRing ring_trk;             // evam_pp_track_device_rois' block (stream runs, item table, classify label set)
 };
 
 namespace {
@@ -4338,14 +4346,16 @@ void evam_pp_destroy(evam_pp* h) {
     }
 #endif
     (void)hipSetDevice(h->device);
-    if (h->ring.have_copy || h->ring_ssd.have_copy || h->pin.cur >= 0) {
+    if (h->ring.have_copy || h->ring_ssd.have_copy || h->ring_trk.have_copy || h->pin.cur >= 0) {
         (void)hipStreamSynchronize(h->stream);
         if (h->ring.have_copy) (void)hipStreamSynchronize(h->ring.copy);
         if (h->ring_ssd.have_copy) (void)hipStreamSynchronize(h->ring_ssd.copy);
+        if (h->ring_trk.have_copy) (void)hipStreamSynchronize(h->ring_trk.copy);
     }
     HipRings b;
     h->ring.release(b);
     h->ring_ssd.release(b);
+    h->ring_trk.release(b);
     h->pin.release(b);
     for (void* p : h->jpeg.buf)
         if (p) (void)hipFree(p);  // waits for kernels that still use it
@@ -4365,7 +4375,7 @@ void evam_pp_destroy(evam_pp* h) {
 int evam_pp_set_stream(evam_pp* h, void* hip_stream) {
     if (!h) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_set_stream: NULL handle");
     hipStream_t ns = reinterpret_cast<hipStream_t>(hip_stream);
-    if (ns != h->stream && (h->ring.cur >= 0 || h->pin.cur >= 0 || h->ring_ssd.cur >= 0)) {
+    if (ns != h->stream && (h->ring.cur >= 0 || h->pin.cur >= 0 || h->ring_ssd.cur >= 0 || h->ring_trk.cur >= 0)) {
         // Order the new stream behind everything already launched on the old one, so the descriptor
         // slots' fences (recorded on the current stream) keep covering earlier kernels.
         HIP_TRY(hipSetDevice(h->device));
@@ -5206,6 +5216,12 @@ int evam_pp_ssd_rois_host(const float* det, int n_items, int k, const evam_image
 int evam_pp_ssd_rois(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
                      int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
                      const evam_roi_list* list) {
+    return evam_pp_ssd_rois_ex(h, det, n_items, k, srcs, xf, tensor_w, tensor_h, threshold, labels, n_labels, list, nullptr);
+}
+
+int evam_pp_ssd_rois_ex(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
+                        int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
+                        const evam_roi_list* list, int32_t* out_labels) {
     if (!h) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_ssd_rois: NULL handle");
     if (int rc = check_ssd_args("evam_pp_ssd_rois", det, n_items, k, srcs, tensor_w, tensor_h, labels, n_labels, list))
         return rc;
@@ -5239,9 +5255,11 @@ int evam_pp_ssd_rois(evam_pp* h, const float* det, int n_items, int k, const eva
     p.n_items = n_items; p.k = k; p.n_labels = n_labels;
     p.TW = tensor_w; p.TH = tensor_h; p.cap = list->cap;
     p.threshold = threshold;
+    p.out_labels = out_labels;
     hipLaunchKernelGGL((evam_pp_ssd_rows<false>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
     hipLaunchKernelGGL(evam_pp_ssd_scan, dim3(1), dim3(kThreads), 0, h->stream, p.item_count, p.item_off, n_items, p.count);
-    hipLaunchKernelGGL((evam_pp_ssd_rows<true>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
+    if (out_labels) hipLaunchKernelGGL((evam_pp_ssd_rows<true, true>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
+    else hipLaunchKernelGGL((evam_pp_ssd_rows<true>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "evam_pp_ssd_rois: kernel launch failed: %s", hipGetErrorString(e));
     return EVAM_PP_OK;
@@ -5352,3 +5370,4 @@ int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, cons
 
 #include "evam_jpeg_api.h"
 #include "evam_jpeg_dec_api.h"
+#include "evam_track_api.h"

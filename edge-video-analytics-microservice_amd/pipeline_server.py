@@ -32,6 +32,9 @@ absent). Each element:
 3. runs the registered model (a torch callable: OpenVINO is not part of this stack);
 4. post-processes (``postproc.py``: transform-mapped boxes, ``tensor_to_label``, gvametaconvert JSON).
 
+``gvatrack`` between them is a stage of its own (:class:`TrackStage`): no model, it gives the regions their object
+ids, which ``reclassify-interval`` is keyed on.
+
 Decode stays upstream. An ``application`` source delivers decoded frames:
 device ``Image``s, or host planes uploaded on arrival.
 """
@@ -387,6 +390,10 @@ class BatchHub:
         self.device_rois = False
         self.device_rois_cap = self.max_batch
         self.fused_batches: list = []  # one dict per detect -> classify batch of that option: which path served it
+        # ... with a gvatrack stage in between: one DeviceTracker per interchangeable tracker configuration, shared by
+        # the device's streams; a stream holds one of its "device_track_streams" slots (default 256) until it ends
+        self.track_streams = 256
+        self._trackers: dict = {}       # TrackStage.track_key() -> (DeviceTracker, [free stream slots])
         self._seq = 0
         self._thread = threading.Thread(target=self._loop, name=f"evam-hub-{device}", daemon=True)
         self._thread.start()
@@ -434,6 +441,37 @@ class BatchHub:
         if r is None:
             r = self._rings[key] = ClipRing(device, size)
         return r
+
+    # The hub's trackers are driven from one host thread at a time, as the tracker ABI asks (include/evam_pp.h): the
+    # device runner's thread launches every fused batch and also ends the streams (Pipeline._end runs there), so
+    # track_slot / release_track_slot and every track call come from that thread. Across handles and HIP streams the
+    # tracker orders its calls itself, by its own event: that is why a reset may go through handle 0 whatever handle
+    # the stream's last tick used.
+    def track_free(self, key) -> int:
+        """Free stream slots of the device tracker for ``key`` (all of them while it does not exist yet)."""
+        t = self._trackers.get(key)
+        return self.track_streams if t is None else len(t[1])
+
+    def track_slot(self, key, tracking_type, pp):
+        """A free stream slot of the device tracker for ``key`` (created on first use through ``pp``), or None when
+        every slot is held."""
+        t = self._trackers.get(key)
+        if t is None:
+            from .preproc import DeviceTracker
+
+            t = self._trackers[key] = (DeviceTracker(pp, self.track_streams, tracking_type),
+                                       list(range(self.track_streams - 1, -1, -1)))
+        return (t[0], t[1].pop()) if t[1] else None
+
+    def release_track_slot(self, key, slot: int):
+        """The stream that held ``slot`` ended: the slot is reset (asynchronously, behind the tracker's last call) and
+        free again."""
+        t = self._trackers.get(key)
+        if t is None:
+            return
+        with self.stream_ctx(0):
+            t[0].reset(self.pp(0), slot)
+        t[1].append(slot)
 
     def submit(self, stage, items, units: int):
         """Queue ``items`` of ``stage`` and block until the batch holding them ran (re-raises its error)."""
@@ -509,6 +547,9 @@ class BatchHub:
             self._stop = True
             self._cv.notify_all()
         self._thread.join(10)
+        for t, _ in self._trackers.values():
+            t.close()
+        self._trackers = {}
         for h in self._pps.values():
             h.close()
         self._pps = {}
@@ -729,6 +770,7 @@ class DeviceRunner:
                 s.wait_stream(torch.cuda.default_stream(hub.device))
             depth = max(len(p.stages) for p, _ in work)
             fused_next = set()  # (pipeline, stage index) of classify stages that ran in their detector's batch
+            admitted: dict = {}  # tracker key -> streams this tick sends to the device tracker for the first time
             for k in range(depth):
                 groups: dict = {}
                 for p, items in work:
@@ -745,10 +787,16 @@ class DeviceRunner:
                         continue
                     if units > 0:
                         key = st.hub_key()
-                        nxt = fusable_classify(p, k, items) if hub.device_rois else None
+                        nxt = fusable_classify(p, k, items, hub, admitted) if hub.device_rois else None
                         if nxt is not None:
-                            key = ("detect+classify", key, nxt.hub_key())
-                            fused_next.add((p, k + 1))
+                            cls, trk = nxt
+                            # a tracked batch holds one source format: a stream must not hop between the device
+                            # tracker and the host's because of the streams it happens to share a tick with; and one
+                            # reclassify-interval (a request parameter, not part of the classify key): the device
+                            # gate of a batch runs with a single interval
+                            key = ("detect+classify", key, cls.hub_key()) + \
+                                ((trk.track_key(), items[0][1].fourcc, cls.reclassify) if trk is not None else ())
+                            fused_next.update((p, j) for j in range(k + 1, k + (3 if trk is not None else 2)))
                         groups.setdefault(key, []).append((p, _Request(st, w, units, event=False)))
                 for key, reqs in groups.items():
                     i = 0
@@ -761,13 +809,15 @@ class DeviceRunner:
                         i = j
                         stage = chunk[0][1].stage
                         fused = key[0] == "detect+classify"
-                        last = k + 1 if fused else k  # the chain's stage this batch ends with
+                        tracked = fused and len(key) > 3
+                        last = k + (2 if tracked else 1) if fused else k  # the chain's stage this batch ends with
                         defer = (hub.inflight > 1 and (fused or hasattr(stage, "launch_batch"))
                                  and all(last == len(p.stages) - 1 for p, _ in chunk))
                         try:
                             if fused:
-                                done = launch_detect_classify(hub, [(r, p.stages[k + 1]) for p, r in chunk],
-                                                              hub.pp(slot), hub.device_rois_cap)
+                                done = launch_detect_classify(
+                                    hub, [(r, p.stages[last], p.stages[k + 1] if tracked else None) for p, r in chunk],
+                                    hub.pp(slot), hub.device_rois_cap)
                                 if done is None:
                                     defer = False  # served by the host path, complete
                                 elif defer:
@@ -1042,6 +1092,14 @@ class ClassifyStage(_InferenceStage):
             if len(self._cache) > 65536:
                 self._cache.clear()
 
+    def prune_cache(self, fi: int, above: int = 1024):
+        """Forget the objects classified ``reclassify-interval`` or more frames before frame ``fi``: no later frame
+        can take their results, so the selection is unchanged. The device tracker keeps each live object's frame for
+        as long as the object lives, so a fused batch keeps this cache small instead of letting it reach the size at
+        which ``finish`` clears it, objects inside their interval included."""
+        if len(self._cache) > above:
+            self._cache = {k: v for k, v in self._cache.items() if fi - v[0] < self.reclassify}
+
     def run_batch(self, reqs, pp):
         """One ROI launch over the regions of every request (hub thread)."""
         frames, rois, owners = self.gather(reqs)
@@ -1107,21 +1165,40 @@ def device_label_ids(labels, object_class):
     return ids
 
 
-def fusable_classify(p, k, items):
-    """The gvaclassify stage that can run in one launch-only batch with the gvadetect stage ``p.stages[k]`` (server
-    option ``device_rois``), or None: it follows directly, classifies every frame and every region (intervals 1), takes
-    planar input, and the frames arrive without regions, so the regions it would select are exactly the detections
-    the device list holds."""
+def fusable_classify(p, k, items, hub=None, admitted=None):
+    """``(the gvaclassify stage, the gvatrack stage between or None)`` that can run in one launch-only batch with the
+    gvadetect stage ``p.stages[k]`` (server option ``device_rois``), or None. The classify stage follows directly or
+    behind one gvatrack stage, classifies on every frame (``inference-interval`` 1) and takes planar input, and the
+    frames arrive without regions, so the regions it would select are exactly the detections the device list holds.
+
+    Without a tracker every region has object id 0, which ``reclassify-interval`` does not gate: any interval runs as
+    interval 1. With one, the ids and the interval's gate run on the device (``HipPreProcessor.track_rois``) on a
+    stream slot of the hub's tracker, which ``launch_detect_classify`` takes once the batch is known to run there. A
+    stream stays with the tracker it started on: one whose first tick cannot be fused (no free slot, frames of several
+    formats, a detector that answers on the host) is tracked on the host for good. ``admitted`` counts, per tracker,
+    the new streams of this tick already answered with yes, so that no more are admitted than slots are free."""
     st = p.stages[k]
     if not isinstance(st, DetectStage) or k + 1 >= len(p.stages):
         return None
-    nxt = p.stages[k + 1]
-    if not isinstance(nxt, ClassifyStage) or nxt.interval != 1 or nxt.reclassify != 1 or nxt.model.layout != "nchw" \
-            or nxt.device != st.device:
+    trk = p.stages[k + 1] if isinstance(p.stages[k + 1], TrackStage) else None
+    if trk is not None and k + 2 >= len(p.stages):
+        return None
+    nxt = p.stages[k + (2 if trk is not None else 1)]
+    if not isinstance(nxt, ClassifyStage) or nxt.interval != 1 or nxt.model.layout != "nchw" or nxt.device != st.device:
         return None
     if any(fr._regions for _, _, fr in items):
         return None
-    return nxt
+    if trk is not None:
+        if trk.mode == "host" or hub is None or len({img.fourcc for _, img, _ in items}) != 1:
+            return None
+        if trk.mode is None:
+            key = trk.track_key()
+            taken = 0 if admitted is None else admitted.get(key, 0)
+            if hub.track_free(key) - taken <= 0:
+                return None
+            if admitted is not None:
+                admitted[key] = taken + 1
+    return nxt, trk
 
 
 def launch_detect_classify(hub, pairs, pp, cap: int):
@@ -1141,8 +1218,8 @@ def launch_detect_classify(hub, pairs, pp, cap: int):
 
     from .preproc import DeviceRoiList, ImageBatch
 
-    det, cls = pairs[0][0].stage, pairs[0][1]
-    run = [it for r, _ in pairs for it in r.items]
+    det, cls, trk = pairs[0][0].stage, pairs[0][1], pairs[0][2]
+    run = [it for r, _, _ in pairs for it in r.items]
     entry = {"frames": len(run), "cap": cap, "fused": False, "reason": None, "count": None,
              "launched": hub.next_seq(), "completed": None}
     hub.fused_batches.append(entry)
@@ -1152,7 +1229,7 @@ def launch_detect_classify(hub, pairs, pp, cap: int):
 
     def prepared():
         reqs = []
-        for r, c in pairs:
+        for r, c, _ in pairs:
             w, units = c.prepare(r.items)
             if units > 0:
                 reqs.append(_Request(c, w, units, event=False))
@@ -1165,6 +1242,9 @@ def launch_detect_classify(hub, pairs, pp, cap: int):
         entry["reason"] = "frames of several formats"
     if entry["reason"]:
         det.attach(run, xfs, raw)
+        for r, _, t in pairs:
+            if t is not None:
+                t.process(r.items)  # the host's tracker, for good; refused for a stream the device tracker serves
         reqs = prepared()
         if reqs:
             cls.run_batch(reqs, pp)
@@ -1180,8 +1260,23 @@ def launch_detect_classify(hub, pairs, pp, cap: int):
         d = d.float().contiguous()
     batch = ImageBatch([img for _, img, _ in run])
     lst = DeviceRoiList(cap, device=d.device)
-    pp.detections_to_rois(d, batch, xfs, det.model.input_size, det.threshold,
-                          device_label_ids(det.labels(), cls.object_class), lst)
+    want = device_label_ids(det.labels(), cls.object_class)
+    every = ids = None
+    if trk is None:
+        pp.detections_to_rois(d, batch, xfs, det.model.input_size, det.threshold, want, lst)
+    else:
+        # every detection (no label filter: the tracker follows them all) into a list that cannot overflow, with its
+        # labels; the tracker's ids for them and the entries due for classification, in list order, into ``lst``
+        every = DeviceRoiList(len(run) * int(d.shape[-2]), device=d.device)
+        labels = torch.empty((every.cap,), dtype=torch.int32, device=d.device)
+        pp.detections_to_rois(d, batch, xfs, det.model.input_size, det.threshold, None, every, out_labels=labels)
+        for _, c, t in pairs:
+            assert c.reclassify == cls.reclassify, "a tracked batch holds one reclassify-interval (its key)"
+            if t.mode is None:
+                t.bind_device(hub, pp)  # the batch runs on the device: the stream takes its slot now
+        table = [(t.dev_slot, fi) for r, _, t in pairs for fi, _, _ in r.items]
+        ids = pp.track_rois(every, labels, trk.dev_tracker, table, "all" if want is None else want, cls.reclassify,
+                            None, lst)
     ctens = cls._tensor(cap)
     pp.convert(batch, ctens, cls.info, rois=lst)
     res = cls.model.fn(ctens)
@@ -1190,6 +1285,16 @@ def launch_detect_classify(hub, pairs, pp, cap: int):
     def complete():
         det.attach(run, xfs, raw)
         count = int(lst.count.cpu().numpy().view(np.uint32)[0])
+        if trk is not None:
+            n_all = int(every.count.cpu().numpy().view(np.uint32)[0])
+            got = ids[:min(n_all, every.cap)].cpu().numpy().view(np.uint32).tolist()
+            tracked = [r for _, img, fr in run for r in (fr._regions or ())
+                       if roi_inside(r.x, r.y, r.w, r.h, img.width, img.height)]
+            if len(tracked) != len(got):
+                raise RuntimeError(f"detect -> track: the device list holds {len(got)} regions, the host builds "
+                                   f"{len(tracked)}")
+            for r, i in zip(tracked, got):
+                r.object_id = i
         reqs = prepared()
         frames, rois, owners = ClassifyStage.gather(reqs)
         if len(owners) != count:
@@ -1201,9 +1306,11 @@ def launch_detect_classify(hub, pairs, pp, cap: int):
             cls.classify_rois(frames, rois[cap:], owners[cap:], pp)
         for q in reqs:
             q.stage.finish(q.items)
+            if trk is not None:
+                q.stage.prune_cache(max(fi for fi, _, _ in q.items))
         entry["count"] = count
         entry["completed"] = hub.next_seq()
-    complete.out = (out, ctens, lst, d)  # what the kernels read and write stays alive until the batch completes
+    complete.out = (out, ctens, lst, d, every, ids)  # what the kernels read and write stays alive until the batch completes
     return complete
 
 
@@ -1401,8 +1508,79 @@ class ActionRecognitionStage(_InferenceStage):
         self.launch_batch(reqs, pp)()
 
 
+class TrackStage:
+    """gvatrack: object ids for the regions of each frame (``Region.object_id``), which the ``reclassify-interval``
+    of a gvaclassify stage downstream keys its cache on.
+
+    The rule is the tracker's of ``include/evam_pp.h`` (greedy matching on integer IoU keys, this project's
+    convention: DL Streamer's tracker is closed), run on the host by ``evam_pp_track_host`` with this stream's state:
+    no model, no device work, nothing to batch across pipelines. ``tracking-type``: ``zero-term-imageless`` (a track
+    dies on its first missed frame) or ``short-term-imageless`` (after 8; the default); ``zero-term`` and
+    ``short-term`` need image features and are refused with ``ERR_UNSUPPORTED`` when the pipeline starts. ``device`` is
+    accepted and ignored.
+
+    A step is taken on every frame the detector upstream ran on (``detect_interval``, set by the pipeline), with or
+    without regions; on a frame it skipped, tracks are neither aged nor emitted again (DL Streamer's short-term types
+    would emit predicted boxes there). The regions ``roi_inside`` accepts take part, in region order, with
+    ``label_id`` as the label; the others keep id 0."""
+
+    batchable = False
+
+    def __init__(self, el: Element, server, device: int, slot: int = 0):
+        self.el = el
+        self.device = device
+        self.slot = slot
+        self.server = server
+        self.cfg = N.track_cfg(el.properties.get("tracking-type"))  # refused here: before anything runs
+        self.detect_interval = 1
+        self._tracker = None
+        # who tracks this stream, fixed by its first tick: "host" (this stage), or "device" (a stream slot of the
+        # hub's DeviceTracker, driven by the fused detect -> track -> classify batches of server option "device_rois")
+        self.mode = None
+        self.dev_tracker = None
+        self.dev_slot = -1
+        self._hub = None
+
+    def track_key(self):
+        """Stages with equal keys share a DeviceTracker."""
+        return ("gvatrack", self.cfg.max_lost, float(self.cfg.iou_threshold))
+
+    def bind_device(self, hub, pp):
+        """Take a stream slot of the hub's tracker (``fusable_classify`` admitted the stream: one is free)."""
+        got = hub.track_slot(self.track_key(), self.el.properties.get("tracking-type"), pp)
+        if got is None:
+            raise RuntimeError("gvatrack: no free stream slot of the device tracker for an admitted stream")
+        self.dev_tracker, self.dev_slot = got
+        self._hub = hub
+        self.mode = "device"
+
+    def process(self, items):
+        """items: list of (frame_index, Image, FrameResult), in stream order."""
+        run = [it for it in items if it[0] % self.detect_interval == 0]
+        if not run:
+            return  # only frames the detector skipped: no step, whoever tracks the stream
+        if self.mode == "device":
+            raise PreProcError(N.ERR_UNSUPPORTED, "gvatrack: this stream's objects are tracked on the device (server option "
+                               "\"device_rois\"), and this batch cannot run there: its frames arrive with regions or in "
+                               "several formats, or the detector's output is not a device [n,K,7] tensor")
+        self.mode = "host"
+        if self._tracker is None:
+            self._tracker = N.HostTracker(cfg=self.cfg)
+        for fi, img, fr in run:
+            regions = [r for r in (fr._regions or ()) if roi_inside(r.x, r.y, r.w, r.h, img.width, img.height)]
+            ids, _ = self._tracker.step(fi, [(r.x, r.y, r.w, r.h) for r in regions], [r.label_id for r in regions])
+            for r, i in zip(regions, ids.tolist()):
+                r.object_id = i
+
+    def close(self):
+        self._tracker = None
+        if self._hub is not None:
+            self._hub.release_track_slot(self.track_key(), self.dev_slot)
+            self._hub = self.dev_tracker = None
+
+
 STAGES = {"gvadetect": DetectStage, "gvaclassify": ClassifyStage, "gvainference": DetectStage,
-          "gvaactionrecognitionbin": ActionRecognitionStage}
+          "gvaactionrecognitionbin": ActionRecognitionStage, "gvatrack": TrackStage}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1537,6 +1715,12 @@ class Pipeline:
         self.build(source, parameters)
         self.stages = [STAGES[e.factory](e, self.server, self.device, self.slot)
                        for e in self.elements if e.factory in STAGES]
+        upstream = 1
+        for st in self.stages:  # a gvatrack stage steps on the frames its detector ran on
+            if isinstance(st, DetectStage):
+                upstream = max(1, st.interval)
+            elif isinstance(st, TrackStage):
+                st.detect_interval = upstream
         self.source = source or {}
         self.destination = destination or {}
         self.state = self.RUNNING
@@ -1913,6 +2097,7 @@ class _Server:
                                                 inflight=int(o.get("inflight", 3)))
                 h.device_rois = bool(o.get("device_rois", False))
                 h.device_rois_cap = max(1, int(o.get("device_rois_cap") or h.max_batch))
+                h.track_streams = max(1, int(o.get("device_track_streams") or 256))
             return h
 
     def runner(self, slot: int = 0) -> DeviceRunner:

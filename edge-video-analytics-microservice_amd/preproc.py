@@ -189,6 +189,48 @@ class DeviceRoiList:
         return self.cap
 
 
+class DeviceTracker:
+    """The gvatrack states of ``n_streams`` streams in device memory (``evam_pp_tracker``), created through the handle
+    ``pp`` and driven by :meth:`HipPreProcessor.track_rois` of any handle of that device: calls through different
+    handles (different streams) are ordered one behind the other on the device by the tracker's own event, and the
+    host never waits. ``tracking_type``: the element property (None: ``short-term-imageless``); ``zero-term`` and
+    ``short-term`` are refused with ``ERR_UNSUPPORTED``."""
+
+    def __init__(self, pp: "HipPreProcessor", n_streams: int, tracking_type=None,
+                 iou_threshold: float = N.TRACK_IOU_THRESHOLD):
+        self.cfg = N.track_cfg(tracking_type, iou_threshold)
+        self._lib = pp._lib
+        self.n_streams = int(n_streams)
+        self.device = pp.device
+        t = ctypes.c_void_p()
+        pp._bind_stream()
+        N.check(self._lib, self._lib.evam_pp_tracker_create(pp._h, self.n_streams, ctypes.byref(self.cfg), ctypes.byref(t)))
+        self._t = t
+
+    def reset(self, pp: "HipPreProcessor", stream: int):
+        """Make stream slot ``stream`` fresh again (its stream ended). Asynchronous on ``pp``'s stream."""
+        pp._bind_stream()
+        N.check(self._lib, self._lib.evam_pp_tracker_reset(pp._h, self._t, int(stream)))
+
+    def read_state(self, pp: "HipPreProcessor", stream: int) -> N.EvamTrackState:
+        """Stream slot ``stream``'s state, behind every call issued so far. Synchronises (diagnostics and tests)."""
+        st = N.EvamTrackState()
+        pp._bind_stream()
+        N.check(self._lib, self._lib.evam_pp_tracker_read(pp._h, self._t, int(stream), ctypes.byref(st)))
+        return st
+
+    def close(self):
+        if getattr(self, "_t", None) and self._t.value:
+            self._lib.evam_pp_tracker_destroy(self._t)
+            self._t = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclass
 class PreProcInfo:
     """Model input pre-processing description (DLS ``InputImageLayerDesc`` from a model-proc)."""
@@ -568,7 +610,7 @@ class HipPreProcessor:
         return Transforms(xf) if want_transform == "lazy" else list(Transforms(xf))
 
     def detections_to_rois(self, det, frames, transforms, tensor_size, threshold: float, labels=None,
-                           out_list: DeviceRoiList | None = None):
+                           out_list: DeviceRoiList | None = None, out_labels=None):
         """The rects a gvaclassify stage crops from a detector's SSD output, written into a device list with no host
         round trip (``evam_pp_ssd_rois``): what ``postproc.parse_ssd_batch`` -> ``detections_to_regions`` ->
         the label filter -> ``pipeline_server.roi_inside`` give on the host, in their order.
@@ -577,7 +619,9 @@ class HipPreProcessor:
         :class:`ImageBatch` or Images; only sizes are read); ``transforms``: what ``convert(..., want_transform=...)``
         returned for the detector's input, or None (plain full-frame resizes); ``tensor_size``: ``(W, H)`` of that
         input; ``labels``: accepted label ids, or None for all; ``out_list``: the list to fill (default: a new one of
-        n * K entries). Returns the list. Asynchronous, as :meth:`convert`."""
+        n * K entries); ``out_labels``: None, or a contiguous int32 device tensor of at least ``out_list.cap`` elements
+        that receives each entry's label id beside its rect (``evam_pp_ssd_rois_ex``; what :meth:`track_rois` takes).
+        Returns the list. Asynchronous, as :meth:`convert`."""
         import numpy as np
 
         torch = self._torch
@@ -595,13 +639,57 @@ class HipPreProcessor:
         xf = N.transforms_array(transforms, n)
         lab = None if labels is None else np.ascontiguousarray(list(labels), dtype=np.int32)
         self._bind_stream()
-        rc = self._lib.evam_pp_ssd_rois(
-            self._h, ctypes.c_void_p(det.data_ptr()), n, k, batch.c_array, xf, int(tensor_size[0]), int(tensor_size[1]),
-            float(threshold), None if lab is None else lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            0 if lab is None else int(lab.size), out_list.c_ref)
+        args = (self._h, ctypes.c_void_p(det.data_ptr()), n, k, batch.c_array, xf, int(tensor_size[0]), int(tensor_size[1]),
+                float(threshold), None if lab is None else lab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                0 if lab is None else int(lab.size), out_list.c_ref)
+        if out_labels is None:
+            rc = self._lib.evam_pp_ssd_rois(*args)
+        else:
+            self._check_i32(out_labels, out_list.cap, "detections_to_rois: out_labels")
+            rc = self._lib.evam_pp_ssd_rois_ex(*args, ctypes.c_void_p(out_labels.data_ptr()))
         if rc:
             N.check(self._lib, rc)
         return out_list
+
+    def _check_i32(self, t, n: int, what: str):
+        torch = self._torch
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+            raise PreProcError(N.ERR_INVALID_ARG, f"{what} must be a contiguous int32 tensor of >= {n} elements, got "
+                                                  f"{t.dtype} {tuple(t.shape)}")
+        self._check_device(t)
+
+    def track_rois(self, lst: DeviceRoiList, labels, tracker: DeviceTracker, items, classify_labels=None,
+                   reclassify: int = 1, out_ids=None, due: DeviceRoiList | None = None):
+        """Object ids for the entries of a device list, and the entries due for classification, with no host round trip
+        (``evam_pp_track_device_rois``: the gvatrack rule of ``include/evam_pp.h``, one workgroup per stream).
+
+        ``lst``: the detections of ``len(items)`` items in item order, as :meth:`detections_to_rois` writes them;
+        ``labels``: int32 device tensor ``[>= lst.cap]``, each entry's label id; ``items``: per item ``(stream slot,
+        frame index)``, every slot's items contiguous and in ascending frame order (else ``ERR_INVALID_ARG``);
+        ``classify_labels``: None (no gate), ``"all"`` or the label ids a classify stage crops; ``reclassify``: its
+        ``reclassify-interval``; ``out_ids``: int32 device tensor ``[>= lst.cap]`` to fill (the bits of uint32 ids;
+        default: a new one); ``due``: None, or the list that receives the due entries in list order (its count is
+        the true total, also past its cap). Returns ``out_ids``. Asynchronous, as :meth:`convert`."""
+        torch = self._torch
+        self._check_i32(labels, lst.cap, "track_rois: labels")
+        if out_ids is None:
+            out_ids = torch.zeros((lst.cap,), dtype=torch.int32, device=lst.device)
+        self._check_i32(out_ids, lst.cap, "track_rois: out_ids")
+        self._check_device(lst.rois)
+        if due is not None:
+            self._check_device(due.rois)
+        n = len(items)
+        tab = (N.EvamTrackItem * max(n, 1))()
+        for i, (s, f) in enumerate(items):
+            tab[i].stream, tab[i].frame = int(s), int(f)
+        keep, ptr, n_set = N.classify_set_args(classify_labels)
+        self._bind_stream()
+        rc = self._lib.evam_pp_track_device_rois(
+            self._h, tracker._t, lst.c_ref, ctypes.c_void_p(labels.data_ptr()), n, tab, ptr, n_set, int(reclassify),
+            ctypes.c_void_p(out_ids.data_ptr()), None if due is None else due.c_ref)
+        if rc:
+            N.check(self._lib, rc)
+        return out_ids
 
     def export_bgr(self, srcs, out=None, color_space: str = "BGR"):
         """The packed ``[N,H,W,3]`` uint8 image of every frame of ``srcs`` at source size, in one launch: the frame

@@ -379,6 +379,112 @@ int evam_pp_decode_jpeg_planes(evam_pp* h, const uint8_t* const* files, const si
 int evam_pp_decode_jpeg_planes_host(const uint8_t* const* files, const size_t* lens, int n,
                                     const evam_image* out, int32_t* status);
 
+/* ---- gvatrack: object ids for detections and the reclassify-interval gate (the reference's `gvadetect ! gvatrack !
+ * gvaclassify` templates, pipelines/object_tracking/person_vehicle_bike and object_line_crossing, with the element
+ * properties tracking-type and reclassify-interval). Symbols and new structs added, no existing struct changed: the ABI
+ * version stays 3.
+ *
+ * DL Streamer's tracker is closed; the rule here is this project's own, in integer arithmetic only, so
+ * the host and the device agree bit for bit. Per stream: next_id (from 1) and EVAM_TRACK_SLOTS track slots. One step
+ * takes the stream's frame index and the frame's detections (label, x, y, w, h) in list order:
+ *   1. only the first EVAM_TRACK_DETS detections take part; the rest get id 0;
+ *   2. a live track and a detection of the same label score key = (inter << 16) / union (integer division; inter the
+ *      area of the rect intersection, union = area_t + area_d - inter, a box side counted as min(max(side, 0), 2^20));
+ *      the pair is a candidate when union > 0 and key >= floor(iou_threshold * 65536);
+ *   3. until no candidate is left among unmatched tracks and detections, the one with the largest key is matched
+ *      (ties: lower slot, then lower detection index);
+ *   4. a match copies the detection's box into the track, sets lost = 0 and gives the detection the track's id;
+ *   5. every unmatched live track gets lost += 1 and is freed when lost > max_lost;
+ *   6. unmatched participating detections, in order, take the lowest free slot (slots freed in 5 included) with
+ *      id = next_id++, lost = 0, classified_at = EVAM_TRACK_NONE; with no free slot the detection gets id 0;
+ *   7. the gate, when a classify label set is given: a detection whose label is in the set is due when its id is 0, or
+ *      its track's classified_at is EVAM_TRACK_NONE, or frame - classified_at >= reclassify; a due detection with an
+ *      id sets classified_at = frame. (What the pipeline's gvaclassify stage does with its per-object cache.)
+ * Frame indices of a stream ascend and stay below EVAM_TRACK_NONE. */
+#define EVAM_TRACK_SLOTS 128
+#define EVAM_TRACK_DETS 128
+#define EVAM_TRACK_NONE 0xFFFFFFFFu
+
+typedef struct evam_track_slot { /* 32 B */
+    uint32_t id;            /* 0: the slot is free */
+    int32_t label;
+    int32_t x, y, w, h;     /* the box of the last match */
+    int32_t lost;           /* frames since the last match */
+    uint32_t classified_at; /* frame index of the last due detection, or EVAM_TRACK_NONE */
+} evam_track_slot;
+
+/* A stream's tracker state (4128 B). A fresh state is all zero except next_id = 1 and every classified_at =
+ * EVAM_TRACK_NONE; evam_pp_track_host initialises a state whose next_id is 0 (zeroed memory) that way itself. */
+typedef struct evam_track_state {
+    uint32_t next_id;
+    uint32_t reserved[7];
+    evam_track_slot slots[EVAM_TRACK_SLOTS];
+} evam_track_state;
+
+/* max_lost: 0 (tracking-type zero-term-imageless) .. 8 (short-term-imageless) and beyond; < 0 is refused.
+ * iou_threshold: 0.3 by default in the pipeline; a value <= 0 makes every same-label pair a candidate. */
+typedef struct evam_track_cfg {
+    int32_t max_lost;
+    float iou_threshold;
+} evam_track_cfg;
+
+/* One item (frame) of a track call: the tracker's stream slot it belongs to and its stream's frame index. */
+typedef struct evam_track_item {
+    int32_t stream;
+    uint32_t frame;
+} evam_track_item;
+
+/* One step of the rule on HOST arrays: dets[n_dets] (src_index is ignored) with labels[n_dets] against *state.
+ * ids: uint32[n_dets]. due: NULL or uint8[n_dets], 1 for a due detection. The gate runs when classify_labels is given
+ * (n_classify_labels >= 0 entries) or when n_classify_labels < 0 with a NULL pointer (every label); a NULL pointer with
+ * n_classify_labels == 0 runs no gate (due is all 0). reclassify >= 1. n_dets >= 0 (NULL arrays allowed when 0).
+ * Needs no GPU. Host-only helper. */
+int evam_pp_track_host(evam_track_state* state, const evam_track_cfg* cfg, uint32_t frame, const evam_roi* dets,
+                       const int32_t* labels, int n_dets, const int32_t* classify_labels, int n_classify_labels,
+                       int reclassify, uint32_t* ids, uint8_t* due);
+
+/* A tracker: the states of n_streams streams (1..65535) in DEVICE memory it owns, all fresh. It belongs to the
+ * device of h; any handle of that device may drive it, and calls through different handles (different HIP streams) are
+ * ordered one behind the other on the device by an event the tracker owns: each call waits for the one before it, in
+ * the order the host issued them, and the host does not wait (but see the due-flag buffer of
+ * evam_pp_track_device_rois). The calls of one tracker come from one host thread at a time. */
+typedef struct evam_pp_tracker evam_pp_tracker;
+int evam_pp_tracker_create(evam_pp* h, int n_streams, const evam_track_cfg* cfg, evam_pp_tracker** out);
+/* Waits for the tracker's last call, then frees it. */
+void evam_pp_tracker_destroy(evam_pp_tracker* t);
+/* Make stream slot `stream` fresh again (its stream ended). Asynchronous on the handle's stream. */
+int evam_pp_tracker_reset(evam_pp* h, evam_pp_tracker* t, int stream);
+/* Copy stream slot `stream`'s state to HOST memory `out`, behind every call issued so far, and wait for it
+ * (diagnostics and tests: the only call here that synchronises). */
+int evam_pp_tracker_read(evam_pp* h, evam_pp_tracker* t, int stream, evam_track_state* out);
+
+/* The rule over a device list. list: the detections of n_items items in item order (entry.src_index = item, ascending,
+ * as evam_pp_ssd_rois writes it); labels: device int32[list->cap], the label of each entry. items: HOST table of
+ * n_items entries; the items of a stream slot must be contiguous in it and in ascending frame order, else
+ * EVAM_PP_ERR_INVALID_ARG (as for a stream slot outside the tracker). Each stream slot in the table takes one step per
+ * item of its own, in table order; an item without entries is a step with no detections.
+ * ids: device uint32[list->cap]; ids[e] receives the id of entry e for e < min(*list->count, list->cap); an entry
+ * whose src_index is outside [0, n_items) and the entries from the count on get 0.
+ * classify_labels (HOST array) / n_classify_labels / reclassify: the gate, as for evam_pp_track_host.
+ * due: NULL, or a second list (other memory than `list`) that receives the due entries, unchanged, in list order: an
+ * ordered compaction with no atomic append. *due->count is the true total even past due->cap (then the first due->cap
+ * are stored); classified_at is set for every due entry, stored or not.
+ * One 256-thread workgroup per stream slot in the table walks that slot's items in order, state and keys in LDS.
+ * Asynchronous on the handle's stream; the host reads no device memory. n_items 1..65535.
+ * One exception to "asynchronous": with a due list the tracker keeps a buffer of list->cap due flags. It grows to the
+ * largest cap seen; growing frees the old buffer, and that free waits for the device's pending work. Callers that
+ * must never wait pass lists of one capacity (or the largest first): the buffer is then allocated once per tracker. */
+int evam_pp_track_device_rois(evam_pp* h, evam_pp_tracker* t, const evam_roi_list* list, const int32_t* labels,
+                              int n_items, const evam_track_item* items, const int32_t* classify_labels,
+                              int n_classify_labels, int reclassify, uint32_t* ids, const evam_roi_list* due);
+
+/* evam_pp_ssd_rois that also writes each accepted row's label, int(label) as the host path truncates it (0 for a label
+ * that is not finite or outside int32), to out_labels[position] (device int32[list->cap]) beside its rect.
+ * out_labels == NULL is evam_pp_ssd_rois itself: the same kernels, the same bytes. */
+int evam_pp_ssd_rois_ex(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs,
+                        const evam_transform* xf, int tensor_w, int tensor_h, float threshold,
+                        const int32_t* labels, int n_labels, const evam_roi_list* list, int32_t* out_labels);
+
 #ifdef __cplusplus
 }
 #endif
