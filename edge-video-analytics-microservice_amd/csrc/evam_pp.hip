@@ -24,6 +24,11 @@
 //         the generic, strip, ROI and wave kernels; interleaved 16-bit output: the generic kernel only).
 //  * Letterbox padding tiles never touch the source. Nothing is MFMA-shaped: the path is HBM-bound
 //    integer gather work (roofline: HBM, 8 TB/s).
+//
+// One translation unit. This file: the seven kernel families, the kernel tables, launch_kernel and resident_per_cu
+// (HipKernels, the planner's HIP backend), HipRings, struct evam_pp, run_impl and the entry points. Included:
+// evam_params.h (kernel-argument structs) and evam_plan.h (the host planner), both HIP-free; the JPEG, JPEG-decode and
+// tracker kernels and entry points (evam_*_kernels.h, evam_*_api.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +50,8 @@
 
 #define EVAM_HD __host__ __device__
 #include "evam_geom.h"
+#include "evam_params.h"
+#include "evam_plan.h"
 #include "evam_rings.h"
 #include "evam_clip_simd.h"
 #include "evam_jpeg_dec.h"
@@ -57,17 +64,6 @@ using namespace evam;
 // ------------------------------------------------------------------------------------------------
 // constants
 // ------------------------------------------------------------------------------------------------
-constexpr int kThreads = 256;
-
-constexpr int kLutBytes = 3 * 256 * 4;
-// Output kind of a kernel instantiation (the OUT template parameter): 0 = u8, 1 = fp32 from the table, 2 = a 2-byte
-// element (fp16 or bf16: the same kernels, only the table's contents differ). The table section keeps 4-byte
-// entries for OUT = 2 with the 16-bit pattern in the low half, so vfinal's byte offsets, the LDS carve and
-// every kLutBytes term of the planners are those of fp32; the kernels read the low u16 of an entry.
-constexpr int out_kind(int out_dtype) {
-    return out_dtype == EVAM_DTYPE_U8 ? 0 : (out_dtype == EVAM_DTYPE_F32 ? 1 : 2);
-}
-constexpr int out_esz(int out) { return out == 1 ? 4 : (out == 2 ? 2 : 1); }
 // Stage-removal diagnostics (bits: 2 no pixel math, 4 no stores, 8 loads only, 16 no loads, 32/64/128 stop
 // early). Compile-time only: a product build is 0, every diagnostic branch folds away, and no environment
 // setting can change results. A build with -DEVAM_PP_ABLATE=bits computes INVALID tensors; evam_pp_create
@@ -94,100 +90,6 @@ constexpr int kKR = kHalf - 128 * kCVR - 16 * kCY;  // the luma term is max(Y,16
 constexpr int kKG = kHalf - 128 * kCVG - 128 * kCUG - 16 * kCY;
 constexpr int kKB = kHalf - 128 * kCUB - 16 * kCY;
 
-// ------------------------------------------------------------------------------------------------
-// device-side descriptors
-// ------------------------------------------------------------------------------------------------
-struct alignas(16) ItemDesc {
-    const uint8_t* plane[3];
-    int32_t pitch[3];
-    int32_t x0, y0, cw, ch;  // effective crop in source pixels
-    int32_t rw, rh, ox, oy;  // resized size, placement in the DW x DH plane
-    int32_t index;    // item index in the call: output slot = slot_offset + index * slot_stride
-    int32_t pad_;
-    double scale_x, scale_y; // OpenCV: 1. / ((double)rw / cw)
-};
-static_assert(sizeof(ItemDesc) == 96, "ItemDesc layout");
-
-struct KParams {
-    const ItemDesc* items;
-    const float* lut;  // [3][256]
-    void* dst;
-    int slot_offset, slot_stride;  // output slot of item i = slot_offset + i * slot_stride
-    int DW, DH;
-    int TW, TH, tiles_x, tiles_per_item, n_tiles;
-    uint32_t tw_magic;  // ceil(2^32 / TW) (TW > 1)
-    int offCol, offRow; // LDS carve: LUT at 0 (fp32 out), column table, row table
-    int color_rgb;
-    uint32_t fill;      // packed u8 fill, output channel order
-};
-
-// Per output column of a tile: absolute byte offsets of the two horizontal taps inside a source row.
-struct alignas(16) ColEntry {  // 16 B
-    int32_t oY0, oY1;  // luma / packed-pixel byte offsets of tap 0 / tap 1 (always valid addresses)
-    int32_t oC0;       // chroma byte offset of tap 0 (NV12: U of the UV pair; I420: U/V plane column)
-    uint16_t a0, a1;   // 11-bit horizontal weights << 4 (see vresize); both 0: the column shows padding
-};
-// Per output row of a tile: byte offsets of the two vertical taps' rows inside the planes.
-struct alignas(16) RowEntry {  // 32 B
-    int32_t y0, y1;   // row offsets in the luma / packed plane (always valid addresses)
-    int32_t c0, c1;   // row offsets in the chroma plane (NV12: UV; I420: U)
-    int32_t b0, b1;   // 11-bit vertical weights << 8 (see vresize); both 0: the row shows padding
-    int32_t v0, v1;   // I420: row offsets in the V plane, which has its own pitch; else 0
-};
-
-// Per-item arguments of the uniform-geometry kernels (staged / wave / rows), carried in the launch's
-// kernel arguments: every item of such a launch shares crop size, resized size and placement, so an
-// item differs only in its frame (planes, pitches), its crop origin and its output slot. Passing them
-// in the kernarg segment means a new set of frames (a decoder's next surfaces, a rotating frame pool)
-// costs no descriptor upload and no cross-stream wait; launches take up to kArgItems items each.
-struct ItemArg {  // 48 B
-    const uint8_t* plane[3];
-    int32_t pitch[3];
-    int32_t x0, y0;   // crop origin in source pixels
-    int32_t index;    // item index in the call: output slot = slot_offset + index * slot_stride
-};
-static_assert(sizeof(ItemArg) == 48, "ItemArg layout");
-constexpr int kArgItems = 64;  // 3 KB of items per launch; the whole parameter block stays < 4 KB
-
-
-struct RParams {
-    ItemArg items[kArgItems];
-    int ox, rw;          // uniform placement / resized width
-    const float* lut;    // [3][256]
-    const XTab* xtab;    // [DW]
-    const YTab* ytab;    // [DH]
-    void* dst;
-    int slot_offset, slot_stride;  // output slot of item i = slot_offset + i * slot_stride
-    int DW, DH;
-    int TW, TH, tiles_x, tiles_per_item;
-    int nsegx;           // TW / 64 column segments per tile row
-    int color_rgb;
-    uint32_t fill;
-};
-
-constexpr int kSlot = 1024;  // bytes of one staged source-row segment = one wave-wide 16 B/lane LDS-DMA
-
-struct SParams {
-    ItemArg items[kArgItems];
-    int ox, rw;          // uniform placement / resized width
-    const float* lut;    // [3][256]
-    const XTab* xtab;    // [DW]
-    const YTab* ytab;    // [DH]
-    void* dst;
-    int slot_offset, slot_stride;  // output slot of item i = slot_offset + i * slot_stride
-    int DW, DH;
-    int TH, tiles_x, tiles_per_item;
-    int offBuf;          // LDS offset of staging buffer 0 (after the LUT)
-    int buf_bytes;       // one staging buffer: 2 R planes x slot_bytes
-    int slot_bytes;      // one staged row segment: the widest 16-byte-aligned footprint of the launch
-    int color_rgb;
-    uint32_t fill;
-    int xcd_remap;       // 1: consecutive tiles land on one XCD (shared halo rows stay in one L2)
-    int ntcol;           // tiles_x when <= kTCols (tcol valid), else 0 (the kernel reads xtab)
-    int2 tcol[16];       // per tile column: crop-relative source columns of its first / last visible
-                         // output column's taps, or (-1, -1) for a tile of padding columns only
-};
-constexpr int kTCols = 16;
 
 // Workgroups are dispatched round-robin over the 8 XCDs (block b runs on XCD b % 8). Remap so each
 // XCD walks a contiguous run of tiles: neighbouring tiles of one frame share source rows at their
@@ -895,7 +797,7 @@ __global__ __launch_bounds__(kThreads) void evam_pp_staged(const SParams P) {
     const uint8_t* p2 = it.plane[2];
     const int pitch0 = it.pitch[0], pitch1 = it.pitch[1], pitch2 = it.pitch[2];
     const int x0 = it.x0, y0 = it.y0, ox = P.ox, rw = P.rw;
-    const int2 tc = P.tcol[min(tx, kTCols - 1)];
+    const ColSpan tc = P.tcol[min(tx, kTCols - 1)];
     const int p_ntcol = P.ntcol, p_index = it.index;
     asm volatile("" ::"s"(p0), "s"(p1), "s"(p2), "s"(pitch0), "s"(pitch1), "s"(pitch2), "s"(x0), "s"(y0),
                  "s"(p_index), "s"(tc.x), "s"(tc.y), "s"(P.dst), "s"(P.slot_offset), "s"(P.slot_stride));
@@ -1214,22 +1116,6 @@ __global__ __launch_bounds__(kThreads) void evam_pp_staged(const SParams P) {
 // ------------------------------------------------------------------------------------------------
 // wave-row kernel (uniform geometry)
 // ------------------------------------------------------------------------------------------------
-struct WParams {
-    ItemArg items[kArgItems];
-    int ox, rw;          // uniform placement / resized width
-    const float* lut;    // [3][256]
-    const XTab* xtab;    // [DW]
-    const YTab* ytab;    // [DH]
-    void* dst;
-    int slot_offset, slot_stride;  // output slot of item i = slot_offset + i * slot_stride
-    int DW, DH;
-    int TH, tiles_x, tiles_per_item;
-    int offBuf;          // LDS offset of the per-wave staging areas (after the LUT)
-    int segY, segC;      // bytes of one staged luma / chroma row segment (multiples of 16)
-    int wave_bytes;      // one wave's staging area (two buffers)
-    int color_rgb;
-    uint32_t fill;
-};
 
 typedef int evam_v2i __attribute__((ext_vector_type(2)));
 typedef int evam_v3i __attribute__((ext_vector_type(3)));
@@ -1673,63 +1559,11 @@ __device__ unsigned long long g_evam_trace[kTraceWGs * kTraceSlots];
 #define EVAM_WTRACE_VAL(k, v) do { } while (0)
 #endif
 
-static_assert(sizeof(evam_roi) == 20, "evam_roi layout");
-
-// One ROI tile in launch order, self-contained: its source frame's planes and size next to the caller's
-// rect, the item index (output slot) and the output rows the tile covers, so a workgroup needs one
-// 64-byte scalar load (one round trip over PCIe from the pinned descriptor slot) before it can resolve
-// the geometry. (A 16-byte record with the frames in the kernel arguments measured slower: the frame
-// lookup is a second dependent load, profiles/r02r_c3_records.txt.)
-struct alignas(64) RoiRec {  // 64 B
-    const uint8_t* plane[3];
-    int32_t pitch[3];
-    uint16_t width, height;   // source frame (<= 32768, validated)
-    int32_t x, y, w, h;       // the caller's rect
-    int32_t item;
-    uint16_t row0, row1;      // output rows [row0, row1) of this tile (DH <= 65535 for split tiles)
-};
-static_assert(sizeof(RoiRec) == 64, "RoiRec layout");
-// The host builds a record as four 16-byte lines: the frame's first 40 bytes (planes, pitches, size; prepared once per
-// source and call), the caller's rect (evam_roi x, y, w, h: 16 contiguous bytes), then the output index and rows.
-static_assert(offsetof(RoiRec, x) == 40 && offsetof(RoiRec, item) == 56 && offsetof(RoiRec, row0) == 60, "RoiRec lines");
-static_assert(offsetof(evam_roi, h) == offsetof(evam_roi, x) + 12, "evam_roi rect");
 struct RecFrame { __m128i l[3]; };  // a record's bytes 0-47 for one source (bytes 40-47 zero)
 
 // ------------------------------------------------------------------------------------------------
 // strip kernel (uniform geometry, 4:2:0 sources, no shared source rows between output rows)
 // ------------------------------------------------------------------------------------------------
-constexpr int kMaxStrips = 32;  // per-strip footprints in the kernel arguments: DW <= 2048
-constexpr int kSfoot = 64;      // footprint entries: strip kernel tile column x 8 + wave (<= 8 columns)
-// One staged row segment of the strip kernel: a strip's footprint is at most one DMA instruction's 64
-// 16-byte chunks, so every LDS offset of the ring is a compile-time immediate. 64-column 4:2:0 strips (PX = 1)
-// use half-size slots (footprints <= 512 B, downscales <= ~7.7x): half the LDS per wave; BGRx rows are four
-// bytes a pixel and always take whole 1 KB slots.
-constexpr int strip_slot(int fmt, int px) { return px == 1 && fmt != kBGRX ? 512 : 1024; }
-
-struct TParams {
-    ItemArg items[kArgItems];
-    double scale_x, scale_y;     // OpenCV: 1. / ((double)rw / cw), 1. / ((double)rh / ch)
-    const float* lut;            // [3][256]
-    void* dst;
-    int slot_offset, slot_stride;  // output slot of item i = slot_offset + i * slot_stride
-    int DW, DH;
-    int cw, ch, rw, rh, ox, oy;  // the launch's crop size, resized size and placement (uniform)
-    int nw;                      // waves (strips) per workgroup
-    int TH, tiles_x, tiles_per_item;  // tile = nw strips x TH rows
-    int wave_bytes;              // one wave's ring: D entries of strip_slot(PX)-byte segments
-    int color_rgb;
-    uint32_t fill;
-    int2 sfoot[kSfoot];          // per strip: crop-relative source columns of the first visible column's
-                                 // first tap and the last visible column's last tap; (-1, -1): padding only
-                                 // (band kernel: per strip; strip kernel: per tile column x 8 + wave)
-    // band kernel only: one wave per (item, band of TH rows, strip); LDS rows of one band
-    int nstrips, units;          // strips per row; waves of work in the launch
-    int segY, segC;              // bytes of one staged luma / chroma row (multiples of 16)
-    int nrY;                     // most luma rows of one band (the chroma rows follow at nrY * segY)
-    int prio;                    // 1: progress-based wave priority (s_setprio 3 -> 0 over the quarters of a wave's rows)
-    int ahead;                   // band kernel: source rows issued ahead of the rows the current output row reads
-};
-static_assert(sizeof(TParams) <= 4000, "strip / band kernel arguments must fit the 4 KB kernarg segment");
 
 // Row-strip kernel for uniform-geometry 4:2:0 batches whose output rows do not share source rows
 // (downscales: C2, C4, C5). Every wave owns one strip of 64 x PX output columns of a tile (lane l holds
@@ -1806,7 +1640,7 @@ __global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
     int g_ox, g_rw, g_oy, g_rh, g_cw, k_ch, k_rgb;
     double k_scale_x, k_scale_y;
     const float* k_lut;
-    int2 sf;
+    ColSpan sf;
     // grid (tile column, tile row, item): every kernel-argument load of the prologue has an address known at
     // entry, so they all go out in one batch (one round trip before the first DMA)
     const int item = blockIdx.z, ty = blockIdx.y;
@@ -2310,7 +2144,7 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
     // so they all go out in one batch (one round trip before the first DMA)
     const int item = blockIdx.z, band = blockIdx.y;
     const ItemArg& it = P.items[item];
-    const int2 sf = P.sfoot[min((int)blockIdx.x * 8 + wave, kSfoot - 1)];
+    const ColSpan sf = P.sfoot[min((int)blockIdx.x * 8 + wave, kSfoot - 1)];
     const int p_nw = P.nw, p_TH = P.TH, p_DH = P.DH, p_DW = P.DW;
     int p_ns = P.nstrips, k_wb = P.wave_bytes;
     const uint8_t* p0 = it.plane[0];
@@ -2690,28 +2524,6 @@ __global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
     }
 #endif
 }
-
-
-#ifndef EVAM_PP_ROI_K
-#define EVAM_PP_ROI_K 6
-#endif
-constexpr int kRoiK = EVAM_PP_ROI_K;  // max pixels per lane per row group in the ROI kernel
-
-struct QParams {
-    const RoiRec* recs;       // this launch's ROI tiles in launch order (largest work first)
-    const float* lut;         // [3][256]
-    void* dst;
-    int DW, DH;
-    int TH;                   // most output rows of one tile (the LDS row table's size)
-    int mode, placement;      // evam_resize_mode, evam_placement
-    int slot_offset, slot_stride;
-    int offXT, offYT, offBuf; // LDS carve: [LUT][XTab x DW][YTab x TH][buf0][buf1]
-    int buf_bytes;            // one staging buffer
-    int color_rgb;
-    uint32_t fill;
-    int prio;                 // progress-based priority (as the strip kernel's), over the quarters of the row groups
-    uint32_t mqw;             // q / QW as mulhi(q, mqw) for the lane quads (QW = DW / PX > 1): ceil(2^32 / QW)
-};
 
 
 template <int N>
@@ -3319,141 +3131,10 @@ void norm_table(const evam_preproc& cfg, void* out) {
     }
 }
 
-
-struct TileCfg {
-    int TW, TH, offCol, offRow, lds;
-};
-
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
-// Tuning and diagnostic knobs. Read from the environment once, when a handle is
-// created (evam_pp_create), never on the per-call path. -1 = the measured heuristic default.
-struct Knobs {
-    int staged = 1, wave = 1, rows = 1, roi = 1;   // kernel families allowed (wave 2 = force)
-    int th = -1, tw = -1, xcd = -1;                // staged / generic tiles, XCD-contiguous order
-    int nsegx = 0;                                 // staged tile width in 64-column segments (0: widest that fits)
-    int stage_r = -1;                              // staged pipeline: rows per group
-    int wth = -1, px = 0, reuse = 1, wave_lds = 40 * 1024;
-    int roi_th = -1, roi_buf = -1, roi_px = 2;     // roi_buf -1: sized for one round; pixels per lane (1 for odd DW)
-    int roi_sort = 1;  // 1: largest estimated bytes first before the stable sort by row groups (alone: equal or
-                       // slower, profiles/r04k_ab_lines.txt; with the snake deal below C3 +1.5-2 %,
-                       // profiles/r05zf_c3_snake_ab.txt)
-    int roi_tail = 4;                              // row tiles per ROI of the uneven tail over the CUs (1: no split)
-    int roi_snake = 1;                             // snake deal of the sorted units over the CUs (0: bands in one direction)
-    int roi_xcd = 0;                               // 1: each frame's ROIs on one XCD, snake-dealt over its CUs (experiment)
-    int strip = 1, strip_th = -1, strip_nw = -1, strip_px = 0;  // strip kernel: allowed (2: forced), rows per
-                                                                // tile, waves, px
-    int strip_pair = 1;                            // strip kernel: paired-tap DMA where the footprints allow it
-    int strip_waves = 16;                          // strip / band kernels: resident waves per CU the tiles are sized for
-    int band = 1, band_px = 0;                     // band kernel: allowed (2: forced), pixels per lane
-    int band_dd = 1;                               // band kernel: six-column lanes where the column table allows
-    int rec_device = 1;                            // ROI records in host-written device memory where mapped (0: pinned host)
-    int prio = 1;                                  // progress-based wave priority (strip, band, ROI kernels): C2 +3 %,
-                                                   // C4 +3 %, C5 +3-5 %, C1 +9 % (profiles/r04k_ab_lines.txt)
-    int band_ahead = 2;                            // band kernel: source rows issued ahead of the current output row's
-                                                   // (64: the whole band at once; 2 measured +2 % on C1)
-    int host_simd = 1;                             // ROI calls: pass 1 on AVX2 (0: scalar)
-    void read() {
-        host_simd = env_int("EVAM_PP_HOST_SIMD", host_simd);
-        prio = env_int("EVAM_PP_PRIO", prio);
-        band_ahead = env_int("EVAM_PP_BAND_AHEAD", band_ahead);
-        band = env_int("EVAM_PP_BAND", band); band_px = env_int("EVAM_PP_BAND_PX", band_px);
-        band_dd = env_int("EVAM_PP_BAND_DD", band_dd);
-        rec_device = env_int("EVAM_PP_REC_DEVICE", rec_device);
-        strip = env_int("EVAM_PP_STRIP", strip); strip_th = env_int("EVAM_PP_STRIP_TH", strip_th);
-        strip_waves = env_int("EVAM_PP_STRIP_WAVES", strip_waves);
-        strip_pair = env_int("EVAM_PP_STRIP_PAIR", strip_pair); strip_nw = env_int("EVAM_PP_STRIP_NW", strip_nw);
-        strip_px = env_int("EVAM_PP_STRIP_PX", strip_px);
-        staged = env_int("EVAM_PP_STAGED", staged); wave = env_int("EVAM_PP_WAVE", wave);
-        rows = env_int("EVAM_PP_ROWS", rows); roi = env_int("EVAM_PP_ROI", roi);
-        th = env_int("EVAM_PP_TH", th); tw = env_int("EVAM_PP_TW", tw); xcd = env_int("EVAM_PP_XCD", xcd);
-        nsegx = env_int("EVAM_PP_NSEGX", nsegx);
-        stage_r = env_int("EVAM_PP_STAGE_R", stage_r);
-        wth = env_int("EVAM_PP_WTH", wth); px = env_int("EVAM_PP_PX", px);
-        reuse = env_int("EVAM_PP_REUSE", reuse); wave_lds = env_int("EVAM_PP_WAVE_LDS", wave_lds);
-        roi_th = env_int("EVAM_PP_ROI_TH", roi_th); roi_buf = env_int("EVAM_PP_ROI_BUF", roi_buf);
-        roi_px = env_int("EVAM_PP_ROI_PX", roi_px); roi_sort = env_int("EVAM_PP_ROI_SORT", roi_sort);
-        roi_tail = env_int("EVAM_PP_ROI_TAIL", roi_tail); roi_snake = env_int("EVAM_PP_ROI_SNAKE", roi_snake);
-        roi_xcd = env_int("EVAM_PP_ROI_XCD", roi_xcd);
-    }
-};
-
-// Tile shape: up to 512 columns (a whole model-input row when it fits) x enough rows for ~4096 output
-// pixels per 256-thread workgroup, so the per-tile table setup is amortised over ~16 pixels per lane.
-// EVAM_PP_TW / EVAM_PP_TH override (tuning).
-TileCfg choose_tiles(int DW, int DH, int out_dtype, const Knobs& k) {
-    TileCfg t{};
-    t.TW = std::min(DW, 512);
-    t.TH = std::max(1, std::min(DH, 4096 / t.TW));
-    if (k.tw > 0) t.TW = std::max(1, std::min(DW, k.tw));
-    if (k.th > 0) t.TH = std::max(1, std::min(DH, k.th));
-    t.offCol = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
-    t.offRow = t.offCol + (int)sizeof(ColEntry) * t.TW;
-    t.lds = t.offRow + (int)sizeof(RowEntry) * t.TH;
-    return t;
-}
-
-struct TabCache {
-    int key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    std::vector<XTab> x;
-    std::vector<YTab> y;
-};
-
-// OpenCV coefficient tables for the uniform-geometry kernel, indexed by output column / row of the
-// DW x DH plane (padding columns / rows get zero weights). Cached: rebuilt only when the geometry changes.
-void build_tables(const Geom& g, int DW, int DH, TabCache& c, XTab* xt, YTab* yt) {
-    const int key[8] = {g.cw, g.ch, g.rw, g.rh, g.ox, g.oy, DW, DH};
-    if (memcmp(key, c.key, sizeof(key)) != 0) {
-        c.x.assign(DW, XTab{});
-        c.y.assign(DH, YTab{});
-        build_tables_into(g, DW, DH, c.x.data(), c.y.data());
-        memcpy(c.key, key, sizeof(key));
-    }
-    memcpy(xt, c.x.data(), sizeof(XTab) * DW);
-    memcpy(yt, c.y.data(), sizeof(YTab) * DH);
-}
-
-struct RowCfg {
-    int TW, TH;
-};
-
-// Row-kernel tile: TW in {512, 256, 128, 64} (whole 64-pixel segments; 4 waves split them) chosen for
-// the least padding lanes, and enough rows for ~4096 pixels per 256-thread workgroup.
-RowCfg choose_row_tiles(int DW, int DH, const Knobs& k) {
-    RowCfg r{512, 8};
-    int best = 1 << 30;
-    for (int tw : {512, 256, 128, 64}) {
-        const int waste = ((DW + tw - 1) / tw) * tw - DW;
-        if (waste < best) { best = waste; r.TW = tw; }
-    }
-    if (k.tw > 0) r.TW = k.tw;
-    if (r.TW != 64 && r.TW != 128 && r.TW != 256 && r.TW != 512) r.TW = 512;
-    r.TH = std::max(1, std::min(DH, k.th > 0 ? k.th : 4096 / r.TW));
-    return r;
-}
-
-// Staged-kernel pipeline shapes: (output rows per group R, staging buffers NBUF). One variant per
-// (format, dtype, column segments) is instantiated for each shape listed here.
-struct StagedShape { int R, nbuf; };
-// (Three staging buffers, 512-column tiles and 2 KB row slots measured neutral or slower for two rounds and were
-// retired in round 5.)
-constexpr StagedShape kStagedShapes[] = {{2, 2}, {1, 2}};
-
-// Valid (column segments, rows per group): four waves split NSEGX x R evenly.
-constexpr bool staged_valid(int nsegx, int R) { return nsegx > 4 ? R == 1 : (nsegx == 4 ? true : R % (4 / nsegx) == 0); }
-
-constexpr bool staged_shape(int R, int nbuf) {
-    for (const StagedShape& ss : kStagedShapes)
-        if (ss.R == R && ss.nbuf == nbuf) return true;
-    return false;
-}
-
 // ---- kernel tables: runtime arguments -> template instantiation, one definition per family ----
-// A family lists the values each template parameter takes (fill), says which combinations are instantiated
-// (built) and where one sits in its table (index). expand_kernels() walks the product of the lists and calls the
+// A family's variants (evam_plan.h: *Variants, shared with the planner's CPU check) say which combinations are
+// instantiated (built) and where one sits in its table (index); here the family adds the values each template
+// parameter takes (fill). expand_kernels() walks the product of the lists and calls the
 // family's put<...>() once per combination; the lookup reads the table through the same index(). Both the
 // occupancy query of a plan and the launch take the pointer from here, so a plan cannot be sized for one
 // instantiation and launched as another, and a new template parameter is one more list and one more digit in
@@ -3464,24 +3145,6 @@ using Fmts = Vals<kNV12, kI420, kBGRX, kBGR>;
 using Outs = Vals<0, 1, 2>;  // out_kind()
 using Bools = Vals<0, 1>;
 using Pxs = Vals<1, 2, 4>;
-constexpr int px_digit(int px) { return px == 1 ? 0 : (px == 2 ? 1 : (px == 4 ? 2 : -1)); }
-
-template <int N>
-constexpr int table_size(const int (&dims)[N]) {
-    int n = 1;
-    for (int d : dims) n *= d;
-    return n;
-}
-// Mixed-radix position of the digits v (v[k] in [0, dims[k])), or -1 when one is out of range.
-template <int N>
-constexpr int table_index(const int (&dims)[N], const int (&v)[N]) {
-    int i = 0;
-    for (int k = 0; k < N; k++) {
-        if (v[k] < 0 || v[k] >= dims[k]) return -1;
-        i = i * dims[k] + v[k];
-    }
-    return i;
-}
 
 template <class Fam, int... Done>
 void expand_kernels(const void** t) { Fam::template put<Done...>(t); }
@@ -3498,9 +3161,7 @@ const void* kernel_at(int index) {
     return index < 0 ? nullptr : t.fn[index];
 }
 
-struct GenericKernels {
-    static constexpr int kDims[] = {4, 3, 2};  // format, output kind, NHWC
-    static constexpr int index(int f, int o, int nhwc) { return table_index(kDims, {f, o, nhwc}); }
+struct GenericKernels : GenericVariants {
     template <int F, int O, int N>
     static void put(const void** t) { t[index(F, O, N)] = (const void*)evam_pp_kernel<F, O, N != 0>; }
     static void fill(const void** t) { expand_kernels<GenericKernels>(t, Fmts{}, Outs{}, Bools{}); }
@@ -3511,9 +3172,7 @@ const void* generic_kernel(int f, int out_dtype, bool nhwc) {
     return fn;
 }
 
-struct RowsKernels {
-    static constexpr int kDims[] = {4, 2};  // format, output kind (u8 / fp32)
-    static constexpr int index(int f, int o) { return table_index(kDims, {f, o}); }
+struct RowsKernels : RowsVariants {
     template <int F, int O>
     static void put(const void** t) { t[index(F, O)] = (const void*)evam_pp_rows<F, O>; }
     static void fill(const void** t) { expand_kernels<RowsKernels>(t, Fmts{}, Bools{}); }
@@ -3524,12 +3183,7 @@ const void* rows_kernel(int f, int out_dtype) {
     return fn;
 }
 
-struct StagedKernels {
-    static constexpr int kDims[] = {4, 2, 2, 3, 1};  // format, output kind (u8 / fp32), R 1 / 2, NSEGX 1 / 2 / 4, NBUF 2
-    static constexpr int index(int f, int o, int R, int nsegx, int nbuf) {
-        return table_index(kDims, {f, o, R - 1, px_digit(nsegx), nbuf - 2});
-    }
-    static constexpr bool built(int R, int nsegx, int nbuf) { return staged_shape(R, nbuf) && staged_valid(nsegx, R); }
+struct StagedKernels : StagedVariants {
     template <int F, int O, int R, int NSEGX, int NBUF>
     static void put(const void** t) {
         if constexpr (built(R, NSEGX, NBUF)) t[index(F, O, R, NSEGX, NBUF)] = (const void*)evam_pp_staged<F, O, R, NSEGX, NBUF>;
@@ -3544,13 +3198,7 @@ const void* staged_kernel(int f, int out_dtype, int R, int nsegx, int nbuf) {
     return fn;
 }
 
-// Interleaved (NHWC) output: PX = 4 only, u8 or fp32 (the planner takes nothing else), see evam_pp_wave.
-struct WaveKernels {
-    static constexpr int kDims[] = {4, 3, 3, 2, 2};  // format, output kind, PX 1 / 2 / 4, REUSE, NHWC
-    static constexpr int index(int f, int o, int px, int reuse, int nhwc) {
-        return table_index(kDims, {f, o, px_digit(px), reuse, nhwc});
-    }
-    static constexpr bool built(int o, int px, int nhwc) { return !nhwc || (px == 4 && o < 2); }
+struct WaveKernels : WaveVariants {
     template <int F, int O, int PX, int R, int N>
     static void put(const void** t) {
         if constexpr (built(O, PX, N)) t[index(F, O, PX, R, N)] = (const void*)evam_pp_wave<F, O, PX, R != 0, N != 0>;
@@ -3565,17 +3213,7 @@ const void* wave_kernel(int f, int out_dtype, int px, bool reuse, bool nhwc) {
     return fn;
 }
 
-// Ring depth: D = 2 (D 1 / 3 / 4 measured slower on C2 and C5, rounds 2-3: profiles/r03f_bench_lines.txt, C2 D 3
-// +2.7 us; the other depths were retired in round 5).
-#ifndef EVAM_PP_STRIP_DEPTH
-#define EVAM_PP_STRIP_DEPTH 2  // A/B builds only (tools/build_variant.sh -DEVAM_PP_STRIP_DEPTH=3)
-#endif
-constexpr int kStripD = EVAM_PP_STRIP_DEPTH;
-// No BGR strip kernel; the interleaved (NHWC) instantiations are fp32 only.
-struct StripKernels {
-    static constexpr int kDims[] = {3, 3, 2, 2, 2};  // format (NV12 / I420 / BGRx), output kind, PX 1 / 2, paired taps, NHWC
-    static constexpr int index(int f, int o, int px, int pr, int nhwc) { return table_index(kDims, {f, o, px - 1, pr, nhwc}); }
-    static constexpr bool built(int o, int nhwc) { return !nhwc || o == 1; }
+struct StripKernels : StripVariants {
     template <int F, int O, int PX, int PR, int N>
     static void put(const void** t) {
         if constexpr (built(O, N)) t[index(F, O, PX, PR, N)] = (const void*)evam_pp_strip<F, O, kStripD, PX, PR, N != 0>;
@@ -3592,13 +3230,7 @@ const void* strip_kernel(int f, int out_dtype, int px, int pr, bool nhwc) {
     return fn;
 }
 
-// NV12 / I420, u8 / fp32; six-column lanes (DD) with PX = 4 only; the interleaved (NHWC) instantiations are u8, PX = 4.
-struct BandKernels {
-    static constexpr int kDims[] = {2, 2, 3, 2, 2};  // format (NV12 / I420), output kind (u8 / fp32), PX 1 / 2 / 4, DD, NHWC
-    static constexpr int index(int f, int o, int px, int dd, int nhwc) {
-        return table_index(kDims, {f, o, px_digit(px), dd, nhwc});
-    }
-    static constexpr bool built(int o, int px, int dd, int nhwc) { return (!dd || px == 4) && (!nhwc || (o == 0 && px == 4)); }
+struct BandKernels : BandVariants {
     template <int F, int O, int PX, int DD, int N>
     static void put(const void** t) {
         if constexpr (built(O, PX, DD, N)) t[index(F, O, PX, DD, N)] = (const void*)evam_pp_band<F, O, PX, DD, N != 0>;
@@ -3613,19 +3245,7 @@ const void* band_kernel(int f, int out_dtype, int px, bool dd, bool nhwc) {
     return fn;
 }
 
-// PX = 2 adjacent pixels per lane by default (round 5; 1 for odd output widths): one dwordx2 store per channel and
-// one row setup per 2 pixels, C3 +3.7 % over PX = 1 on one box (profiles/r05p_c3_roi_px_rmax_ab.txt; PX = 4 equals
-// PX = 1 there, round 2 measured it 8 % slower: lanes 4 pixels apart spread their LDS tap reads over more dwords).
-// (Three staging buffers, EVAM_PP_ROI_NBUF=3, measured neutral or slower for two rounds: retired in round 5.)
-// The device-list siblings (DEV): PX = 2, or 1 for odd output widths (EVAM_PP_ROI_PX = 4 is not built for them).
-constexpr int roi_px(int px, int DW, bool dev) {
-    if (dev) return (px == 2 || px == 4) && DW % 2 == 0 ? 2 : 1;
-    return (px == 4 || px == 2) && DW % px == 0 ? px : 1;
-}
-struct RoiKernels {
-    static constexpr int kDims[] = {4, 3, 3, 2};  // format, output kind, PX 1 / 2 / 4, DEV (two staging buffers each)
-    static constexpr int index(int f, int o, int px, int dev) { return table_index(kDims, {f, o, px_digit(px), dev}); }
-    static constexpr bool built(int px, int dev) { return !dev || px != 4; }
+struct RoiKernels : RoiVariants {
     template <int F, int O, int PX, int DEV>
     static void put(const void** t) {
         if constexpr (built(PX, DEV)) t[index(F, O, PX, DEV)] = (const void*)evam_pp_roi<F, O, PX, 2, DEV != 0>;
@@ -3670,432 +3290,16 @@ int resident_per_cu(const void* fn, int lds, int threads = kThreads) {
     return n;
 }
 
-// What the launches of one uniform-geometry format group share. A plan_* function fills the kernel its plan was
-// sized for (from the family's table), the workgroup size, the dynamic LDS and the grid of a launch of n items:
-// (gx, gy, n) where gy > 0, else n * tiles_per_item workgroups. plan_uniform adds the family and the parameter
-// struct that plan filled.
-struct LaunchPlan {
-    uint32_t family = 0;     // the family's EVAM_KERNEL_* bit (0: no uniform-geometry kernel serves the group)
-    const void* fn = nullptr;
-    int block = kThreads, lds = 0;
-    int gx = 0, gy = 0, tiles_per_item = 0;
-    void* params = nullptr;  // TParams (strip, band), WParams, SParams or RParams
-    ItemArg* items = nullptr;  // its items[kArgItems]
+// HIP backend of the planner (evam_plan.h): the families' lookups above and the occupancy query.
+struct HipKernels {
+    static const void* rows(int f, int out_dtype) { return rows_kernel(f, out_dtype); }
+    static const void* staged(int f, int out_dtype, int R, int nsegx, int nbuf) { return staged_kernel(f, out_dtype, R, nsegx, nbuf); }
+    static const void* wave(int f, int out_dtype, int px, bool reuse, bool nhwc) { return wave_kernel(f, out_dtype, px, reuse, nhwc); }
+    static const void* strip(int f, int out_dtype, int px, int pr, bool nhwc) { return strip_kernel(f, out_dtype, px, pr, nhwc); }
+    static const void* band(int f, int out_dtype, int px, bool dd, bool nhwc) { return band_kernel(f, out_dtype, px, dd, nhwc); }
+    static const void* roi(int f, int out_dtype, int px, bool dev) { return roi_kernel(f, out_dtype, px, dev); }
+    static int resident(const void* fn, int lds) { return resident_per_cu(fn, lds); }
 };
-
-// Wave-row kernel plan for a uniform-geometry group: pixels per lane PX (the widest whose staging
-// fits the LDS budget and divides DW), the exact per-tile footprint from the host tables, REUSE when
-// consecutive output rows share source rows, and a tile height that gives every CU enough workgroups.
-// The kernel stages each item's footprint from that item's own crop origin x0, and the number of
-// 16-byte chunks a footprint spans depends on x0's alignment: the segments are sized for the worst
-// case over every residue x0 mod 32 present in the group (x0_mask bit r), which covers the 16-byte
-// phase of every plane (luma / packed at bpp 1, 3, 4; NV12 chroma 2 (x >> 1); I420 chroma x >> 1).
-bool plan_wave(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-               const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool nhwc, WParams& w, bool& reuse, LaunchPlan& k) {
-    const int npc = f == kI420 ? 2 : (f == kNV12 ? 1 : 0);
-    const int lut = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
-    const int budget = kn.wave_lds;
-    const int want_px = nhwc ? 4 : kn.px;  // the interleaved variant exists for PX = 4 alone
-    int px = 0, lds = 0;
-    w = WParams{};
-    if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
-    reuse = false;
-    for (int Y = 0; Y + 1 < DH; Y++) {
-        const bool pad0 = (yt[Y].b0 | yt[Y].b1) == 0, pad1 = (yt[Y + 1].b0 | yt[Y + 1].b1) == 0;
-        if (!pad0 && !pad1 && yt[Y + 1].r0 <= yt[Y].r1) { reuse = true; break; }
-    }
-    if (kn.reuse == 0) reuse = false;
-    px = 0;
-    for (int cand : {4, 2, 1}) {
-        if (want_px && cand != want_px) continue;
-        if (cand > 1 && DW % cand) continue;
-        const int tw = 64 * cand;
-        int mY = 0, mC = 0;
-        wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, tw, mY, mC);
-        const int segY = std::max(16, 16 * mY), segC = npc ? std::max(16, 16 * mC) : 0;
-        const int wave_bytes = 2 * (2 * segY + 2 * npc * segC);
-        const int need = lut + 4 * wave_bytes;
-        if (need > budget && !(want_px && need <= 64 * 1024)) continue;
-        px = cand;
-        w.segY = segY;
-        w.segC = segC;
-        w.wave_bytes = wave_bytes;
-        w.offBuf = lut;
-        lds = need;
-        break;
-    }
-    if (!px) return false;
-    w.DW = DW; w.DH = DH;
-    w.tiles_x = (DW + 64 * px - 1) / (64 * px);
-    // Rows per wave: enough that the whole grid is resident at once (one round: a second round repeats
-    // every workgroup's prologue latency at the tail), counting at most 4 resident workgroups per CU —
-    // longer per-wave row runs amortise the prologue better than more waves hide latency. C1: 16-row
-    // tiles at the 5 workgroups per CU its registers allow ran 1.6 rounds, 31.9 us; 28-row tiles (one
-    // round at 5 per CU) 31.6 us; 32-row tiles (one round at 4 per CU) 29.6 us (profiles/r02r_c1_sweep.txt).
-    k.fn = wave_kernel(f, out_dtype, px, reuse, nhwc);
-    const int per_cu = std::min(4, resident_per_cu(k.fn, lds));
-    const int64_t slots = (int64_t)n_cu * per_cu;
-    int64_t rpw = ((int64_t)count * w.tiles_x * DH + 4 * slots - 1) / (4 * slots);
-    rpw = std::max<int64_t>(2, std::min<int64_t>(32, rpw));
-    w.TH = std::max(1, std::min(std::min(DH, 4 * 64), kn.wth > 0 ? kn.wth : (int)(4 * rpw)));  // <= 64 rows per wave
-    w.tiles_per_item = w.tiles_x * ((DH + w.TH - 1) / w.TH);
-    if ((int64_t)count * w.tiles_per_item > 0x7FFFFFFF) return false;
-    k.block = kThreads;
-    k.lds = lds;
-    k.gy = 0;
-    k.tiles_per_item = w.tiles_per_item;
-    return true;
-}
-
-// Strip-kernel plan for a uniform 4:2:0 group (fills everything in TParams but the items, LUT, output
-// and colour fields).
-//  * Pixels per lane PX: 2 (128-column strips: one ~480-byte DMA segment per source row at 3.75x) where
-//    the output has at least 4 such strips per row and a strip's footprint fits one 1 KB DMA instruction;
-//    the strip pattern's data movement alone is 3 us faster at 128 columns than at 64
-//    (profiles/r03c_strip_bw.txt).
-//  * Waves per workgroup: 4..8 strips with the fewest idle waves.
-//  * Tile height: about EVAM_PP_STRIP_WAVES (16) waves per CU over the whole launch (the data-movement
-//    microbenchmark's best: fewer, longer-lived waves beat a full 32), at most 64 rows (the lane-held row
-//    table).
-//  * Ring depth: kStripD = 2.
-//  * Paired taps (pr): both source rows of a plane in one LDS-DMA instruction when every strip's footprint is at
-//    most 32 chunks (512 B) per row (I420 chroma: 16, four segments per instruction): 2 instructions per row
-//    instead of 4 (NV12) or 6 (I420), 1 instead of 2 (BGRx). EVAM_PP_STRIP_PAIR=0 keeps one row per instruction.
-// Returns false when the geometry does not suit it: outputs wider than kMaxStrips strips, footprints over
-// 1 KB per strip, or consecutive output rows that share source rows (vertical upscales: the wave kernel's
-// REUSE path).
-bool plan_strip(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-                const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool pair_ok, bool nhwc, TParams& p, LaunchPlan& k) {
-    if (f != kNV12 && f != kI420 && f != kBGRX) return false;
-    int shared = 0, vis = 0;
-    for (int Y = 0; Y + 1 < DH; Y++) {
-        const bool pad0 = (yt[Y].b0 | yt[Y].b1) == 0, pad1 = (yt[Y + 1].b0 | yt[Y + 1].b1) == 0;
-        if (pad0 || pad1) continue;
-        vis++;
-        shared += yt[Y + 1].r0 <= yt[Y].r1;
-    }
-    if (kn.strip != 2 && shared * 8 > vis) return false;  // more than 1 in 8 rows re-stages a row
-    if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
-    const int npc = f == kI420 ? 2 : (f == kBGRX ? 0 : 1);
-    int mY = 0, mC = 0;
-    int px = 0;
-    for (int cand : {2, 1}) {
-        if (kn.strip_px > 0 && cand != kn.strip_px) continue;
-        // 128-column strips only where they still give a workgroup 4 strips per row: C5 (224 columns: two
-        // 128-column strips, the second 3/4 full) runs 13.0 us in four 64-column strips and 15.6 us in
-        // two 128-column ones (profiles/r03g_c5_px.txt)
-        if (cand == 2 && (DW + 127) / 128 < 4 && kn.strip_px != 2) continue;
-        wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, 64 * cand, mY, mC);
-        const int cap = strip_slot(f, cand) / 16;  // chunks of one slot
-        if (mY <= cap && mC <= cap) { px = cand; break; }
-    }
-    if (!px) return false;
-    const int nstrips = (DW + 64 * px - 1) / (64 * px);
-    if (nstrips > kMaxStrips) return false;
-    const int pr = kn.strip_pair && pair_ok && mY <= 32 && (npc == 0 || (npc == 1 && mC <= 32) || (npc == 2 && mC <= 16)) ? 1 : 0;
-    // one ring entry: 2 luma + 2 x npc chroma segments (paired: 1 KB per plane group)
-    const int grp_bytes = pr ? (npc ? 2048 : 1024) : (2 + 2 * npc) * strip_slot(f, px);
-    int nw = 4, best = 1 << 30;
-    for (int c = 4; c <= 8; c++) {
-        const int idle = (nstrips + c - 1) / c * c - nstrips;
-        if (idle < best) { best = idle; nw = c; }
-    }
-    if (nstrips < 4) nw = nstrips;
-    if (kn.strip_nw > 0) nw = std::min(8, kn.strip_nw);
-    p.nw = nw;
-    p.tiles_x = (nstrips + nw - 1) / nw;
-    const int lut_static = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 16;  // the kernel's static LDS
-    const int wg_target = std::max(1, std::min(32, kn.strip_waves) / nw);
-    p.wave_bytes = kStripD * grp_bytes;
-    const int lds = nw * p.wave_bytes + 16;  // dynamic LDS; + 16: a right-edge tap reads past its footprint (weight 0)
-    if (lds + lut_static > 64 * 1024) return false;
-    k.fn = strip_kernel(f, out_dtype, px, pr, nhwc);
-    const int res = std::max(1, std::min(wg_target, resident_per_cu(k.fn, lds)));
-    const int64_t slots = (int64_t)n_cu * res;
-    const int64_t work = (int64_t)std::min(count, kArgItems) * p.tiles_x * DH;
-    int th = (int)std::max<int64_t>(1, (work + slots - 1) / slots);
-    th = std::max(th, std::min(DH, kStripD));
-    if (kn.strip_th > 0) th = kn.strip_th;
-    p.TH = std::max(1, std::min(std::min(DH, 64), th));
-    p.tiles_per_item = p.tiles_x * ((DH + p.TH - 1) / p.TH);
-    p.DW = DW; p.DH = DH;
-    p.cw = g.cw; p.ch = g.ch; p.rw = g.rw; p.rh = g.rh; p.ox = g.ox; p.oy = g.oy;
-    p.scale_x = 1. / ((double)g.rw / g.cw);
-    p.scale_y = 1. / ((double)g.rh / g.ch);
-    const int sw = 64 * px;
-    for (int k = 0; k < kSfoot; k++) {  // entry tile column x 8 + wave (nw <= 8, tiles_x <= 8)
-        const int tx = k >> 3, w = k & 7, s = tx * nw + w;
-        const int Xv0 = std::max(s * sw, g.ox), Xv1 = std::min(std::min(s * sw + sw, DW), g.ox + g.rw) - 1;
-        p.sfoot[k] = w < nw && s < nstrips && Xv0 <= Xv1 ? int2{xt[Xv0].s0, xt[Xv1].s1} : int2{-1, -1};
-    }
-    if ((p.tiles_x - 1) * 8 + nw > kSfoot) return false;
-    if ((int64_t)std::min(count, kArgItems) * p.tiles_per_item > 0x7FFFFFFF) return false;
-    // grid (tile column, tile row, item), dispatched in that order (the C2 data movement in the strip pattern takes
-    // 1.7 us longer with each XCD on its own run of tiles, profiles/r03c_strip_bw.txt)
-    k.block = 64 * nw;
-    k.lds = lds;
-    k.gx = p.tiles_x;
-    k.gy = (DH + p.TH - 1) / p.TH;
-    k.tiles_per_item = p.tiles_per_item;
-    return true;
-}
-
-
-// Band-kernel plan for a uniform 4:2:0 group whose consecutive output rows share source rows (vertical
-// upscales, C1). Fills the geometry, strips, bands and LDS fields of TParams (not items, LUT, output,
-// colour).
-//  * PX: the widest of 4 / 2 / 1 adjacent columns per lane that divides DW and whose strip footprint fits
-//    one DMA instruction (64 chunks) per row.
-//  * Band height TH: about EVAM_PP_STRIP_WAVES (16) waves per CU over the launch (one round), at most 64
-//    (the lane-held row table), lowered until the band's staged rows fit the LDS.
-//  * LDS per wave: the most luma rows any band reads (nrY, from the host's row table) and the chroma rows
-//    they can span at either crop-origin parity (nrY / 2 + 1).
-// Returns false for geometries it does not suit (fewer than 1 in 8 rows sharing source rows, footprints
-// over 1 KB, outputs wider than kMaxStrips strips).
-bool plan_band(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-               const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool nhwc, TParams& p, LaunchPlan& k) {
-    if (f != kNV12 && f != kI420) return false;
-    int shared = 0, vis = 0;
-    for (int Y = 0; Y + 1 < DH; Y++) {
-        const bool pad0 = (yt[Y].b0 | yt[Y].b1) == 0, pad1 = (yt[Y + 1].b0 | yt[Y + 1].b1) == 0;
-        if (pad0 || pad1) continue;
-        vis++;
-        shared += yt[Y + 1].r0 <= yt[Y].r1;
-    }
-    if (kn.band != 2 && shared * 8 <= vis) return false;
-    if (!x0_mask) x0_mask = 1u << (g.x0 & 31);
-    const int npc = f == kI420 ? 2 : 1;
-    int mY = 0, mC = 0;
-    int px = 0, nw = 0, lds = 0;
-    for (int cand : {4, 2, 1}) {
-        if (kn.band_px > 0 && cand != kn.band_px) continue;
-        if (nhwc && cand != 4) continue;  // the interleaved variant exists for PX = 4 alone
-        if (DW % cand) continue;
-        wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, 64 * cand, mY, mC);
-        if (mY <= 64 && mC <= 64) { px = cand; break; }
-    }
-    if (!px) return false;
-    const int nstrips = (DW + 64 * px - 1) / (64 * px);
-    if (nstrips > kMaxStrips) return false;
-    p.segY = 16 * std::max(1, mY);
-    p.segC = 16 * std::max(1, mC) * npc;  // I420: the U and V rows side by side
-    const int lut_static = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 16;
-    const int per_launch = std::min(count, kArgItems);
-    const int64_t want = (int64_t)std::max(1, std::min(64, kn.strip_waves)) * n_cu;
-    const int64_t band_rows = (int64_t)per_launch * nstrips * DH;
-    // Small batches (fewer band rows than the waves the chip is sized for: C1 at 1-4 frames) run faster on the wave
-    // kernel: 7.4 vs 8.1 us per launch at 1, 2 and 4 frames, while at 8 frames the band kernel is 19 % ahead
-    // (profiles/r04i_c1_small_batch_ab.txt)
-    if (band_rows <= want && kn.band != 2 && kn.strip_th <= 0) return false;
-    int th = (int)std::max<int64_t>(2, (band_rows + want - 1) / want);
-    if (kn.strip_th > 0) th = kn.strip_th;
-    th = std::max(1, std::min(std::min(DH, 64), th));
-    for (;; th--) {
-        int nrY = 1;
-        for (int Y0 = 0; Y0 < DH; Y0 += th) {
-            int lo = -1, hi = -1;
-            for (int Y = Y0; Y < std::min(DH, Y0 + th); Y++) {
-                if ((yt[Y].b0 | yt[Y].b1) == 0) continue;  // letterbox row
-                if (lo < 0) lo = yt[Y].r0;
-                hi = yt[Y].r1;
-            }
-            if (lo >= 0) nrY = std::max(nrY, hi - lo + 1);
-        }
-        p.nrY = nrY;
-        p.wave_bytes = nrY * p.segY + (nrY / 2 + 1) * p.segC;
-        nw = std::min(4, nstrips);  // a workgroup: up to four strips of one band
-        lds = nw * p.wave_bytes + 16;  // + 16: a right-edge tap reads past its footprint (weight 0)
-        if (lds + lut_static <= 64 * 1024 && nrY <= 64) break;  // <= 64 rows: one lane of the wait table per row
-        if (th == 1) return false;
-    }
-    p.TH = th;
-    p.nstrips = nstrips;
-    p.tiles_per_item = nstrips * ((DH + th - 1) / th);  // wave units per item
-    p.DW = DW; p.DH = DH;
-    p.cw = g.cw; p.ch = g.ch; p.rw = g.rw; p.rh = g.rh; p.ox = g.ox; p.oy = g.oy;
-    p.scale_x = 1. / ((double)g.rw / g.cw);
-    p.scale_y = 1. / ((double)g.rh / g.ch);
-    p.nw = nw;
-    p.tiles_x = (nstrips + nw - 1) / nw;  // strip groups
-    if ((p.tiles_x - 1) * 8 + nw > kSfoot) return false;
-    const int sw = 64 * px;
-    for (int k = 0; k < kSfoot; k++) {  // entry strip group x 8 + wave
-        const int w = k & 7, s = (k >> 3) * nw + w;
-        const int Xv0 = std::max(s * sw, g.ox), Xv1 = std::min(std::min(s * sw + sw, DW), g.ox + g.rw) - 1;
-        p.sfoot[k] = w < nw && s < nstrips && Xv0 <= Xv1 ? int2{xt[Xv0].s0, xt[Xv1].s1} : int2{-1, -1};
-    }
-    const bool dd = px == 4 && kn.band_dd && band_six_columns(xt, DW, x0_mask);
-    k.fn = band_kernel(f, out_dtype, px, dd, nhwc);
-    k.block = 64 * nw;
-    k.lds = lds;
-    k.gx = p.tiles_x;
-    k.gy = (DH + th - 1) / th;
-    k.tiles_per_item = p.tiles_per_item;
-    return (int64_t)per_launch * p.tiles_per_item <= 0x7FFFFFFF;
-}
-
-// Staged-kernel plan for a uniform group (u8 / fp32, planar): fills the geometry, tile and LDS fields of SParams.
-// Returns false where no tile width fits (the row kernel serves those) or EVAM_PP_STAGED=0.
-bool plan_staged(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-                 const YTab* yt, uint32_t x0_mask, const Knobs& kn, SParams& sp, LaunchPlan& k) {
-    (void)yt;
-    // Tile width: the widest of 256 / 128 columns whose staged row segment (the exact widest footprint of
-    // any tile and crop origin of this group) fits the kernel's 1 KB slot.
-    auto seg_bytes = [&](int tw) {
-        int mY = 0, mC = 0;
-        wave_segments(f, g.ox, g.rw, DW, xt, x0_mask, tw, mY, mC);
-        return 16 * std::max(1, std::max(mY, mC));
-    };
-    int nsegx = 0;
-    if (kn.staged)
-        for (int n : {4, 2}) {  // (64 columns would need R % 4 == 0: the row kernel serves those)
-            if (seg_bytes(64 * n) <= kSlot) { nsegx = n; break; }
-        }
-    if (nsegx && kn.nsegx > 0 && kn.nsegx < nsegx && 2 % (4 / kn.nsegx) == 0) nsegx = kn.nsegx;
-    if (!nsegx) return false;
-    // Pipeline shape: R output rows per group, NBUF staging buffers (NBUF - 1 groups of DMA in
-    // flight).
-    int R = kn.stage_r > 0 ? kn.stage_r : 2, nbuf = 2;
-    if (!staged_shape(R, nbuf) || !staged_valid(nsegx, R)) { R = 2; nbuf = 2; }
-    sp = SParams{};
-    sp.DW = DW; sp.DH = DH;
-    const int tw = 64 * nsegx;
-    sp.tiles_x = (DW + tw - 1) / tw;
-    // ~4096 pixels per workgroup, but short enough tiles that small batches still put
-    // 8 workgroups on every CU (a whole clip-ring step is only 32 x 224 x 224 pixels).
-    // At most 16 rows: C4 (tw 128) runs 3-7 % faster at 16 than at 32 (profiles/r01ad_sweep_th*.txt).
-    int th = std::max(2, std::min(16, 4096 / tw));
-    const int64_t cols = (int64_t)std::min(count, kArgItems) * sp.tiles_x;
-    const int64_t want = 8 * (int64_t)n_cu;
-    if (cols * ((DH + th - 1) / th) < want) th = (int)std::max<int64_t>(2, cols * DH / want);
-    sp.TH = std::max(1, std::min(std::min(DH, 64), kn.th > 0 ? kn.th : th));  // <= 64: lane-held rows
-    sp.TH = std::min(64, (sp.TH + R - 1) / R * R);
-    sp.tiles_per_item = sp.tiles_x * ((DH + sp.TH - 1) / sp.TH);
-    const int np = f == kI420 ? 3 : (f == kNV12 ? 2 : 1);
-    sp.offBuf = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
-    sp.slot_bytes = seg_bytes(tw);  // <= the kernel's SLOT_MAX (tile choice above)
-    sp.buf_bytes = 2 * R * np * sp.slot_bytes;
-    sp.ntcol = sp.tiles_x <= kTCols ? sp.tiles_x : 0;
-    for (int c = 0; c < sp.ntcol; c++) {
-        const int Xv0 = std::max(c * tw, g.ox), Xv1 = std::min(std::min(c * tw + tw, DW), g.ox + g.rw) - 1;
-        sp.tcol[c] = Xv0 <= Xv1 ? int2{xt[Xv0].s0, xt[Xv1].s1} : int2{-1, -1};
-    }
-    k.fn = staged_kernel(f, out_dtype, R, nsegx, nbuf);
-    k.block = kThreads;
-    k.lds = sp.offBuf + nbuf * sp.buf_bytes;
-    k.gy = 0;
-    k.tiles_per_item = sp.tiles_per_item;
-    return true;
-}
-
-// Row-kernel plan for a uniform group (u8 / fp32, planar): the tiles of choose_row_tiles. Serves every geometry.
-bool plan_rows(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-               const YTab* yt, uint32_t x0_mask, const Knobs& kn, RParams& r, LaunchPlan& k) {
-    (void)g; (void)count; (void)n_cu; (void)xt; (void)yt; (void)x0_mask;
-    const RowCfg rc = choose_row_tiles(DW, DH, kn);
-    r = RParams{};
-    r.DW = DW; r.DH = DH;
-    r.TW = rc.TW; r.TH = rc.TH;
-    r.tiles_x = (DW + rc.TW - 1) / rc.TW;
-    r.tiles_per_item = r.tiles_x * ((DH + rc.TH - 1) / rc.TH);
-    r.nsegx = rc.TW / 64;
-    k.fn = rows_kernel(f, out_dtype);
-    k.block = kThreads;
-    k.lds = out_dtype == EVAM_DTYPE_F32 ? kLutBytes : 0;
-    k.gy = 0;
-    k.tiles_per_item = r.tiles_per_item;
-    return true;
-}
-
-// The parameter structs of a uniform group's plan that are not kept on the handle (TParams is: 3.5 KB).
-struct UniformParams {
-    WParams w;
-    SParams s;
-    RParams r;
-};
-
-// The kernel choice for a uniform-geometry format group, in the one place that holds its order and guards:
-// strip, then band, then wave, then staged, then rows; the first family that is allowed (the EVAM_PP_STRIP / _BAND /
-// _WAVE / _STAGED knobs; 2 forces strip, band or wave past the others), instantiated for the output (layout,
-// element size) and whose plan takes the geometry serves the group. run_impl asks twice with the same arguments:
-// ahead of the descriptor block for interleaved and 16-bit groups (family 0: the generic kernel serves the group,
-// which needs its descriptors in the block), and at the launch for every uniform group.
-//  * strip: planar in every element type; interleaved in fp32 (12-byte stores, dword-aligned as the elements are).
-//  * band: u8 / fp32 planar; interleaved u8 with four-pixel stores where they are aligned (nhwc_wave_ok).
-//  * wave: where consecutive output rows share source rows (vertical upscale: REUSE), forced, or interleaved (four-
-//    pixel stores, nhwc_wave_ok); for downscales the staged kernel's deeper shared staging is faster.
-//  * staged, rows: planar u8 / fp32 only (not instantiated for 2-byte elements or interleaved stores).
-LaunchPlan plan_uniform(int f, const Geom& g, int DW, int DH, int count, int out_dtype, int n_cu, const XTab* xt,
-                        const YTab* yt, uint32_t x0_mask, const Knobs& kn, bool pair_ok, bool nhwc, bool nhwc_wave_ok,
-                        TParams& t, UniformParams& u) {
-    const bool half = out_kind(out_dtype) == 2;
-    LaunchPlan k;
-    bool reuse = false;
-    if (kn.strip && kn.wave != 2 && (!nhwc || out_dtype == EVAM_DTYPE_F32) &&
-        plan_strip(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, pair_ok, nhwc, t, k)) {
-        k.family = EVAM_KERNEL_STRIP; k.params = &t; k.items = t.items;
-    } else if (kn.band && kn.wave != 2 && kn.strip != 2 && !half && (!nhwc || (out_dtype == EVAM_DTYPE_U8 && nhwc_wave_ok)) &&
-               plan_band(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, nhwc, t, k)) {
-        k.family = EVAM_KERNEL_BAND; k.params = &t; k.items = t.items;
-    } else if (kn.wave && (!nhwc || nhwc_wave_ok) &&
-               plan_wave(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, nhwc, u.w, reuse, k) &&
-               (reuse || kn.wave == 2 || nhwc)) {
-        k.family = EVAM_KERNEL_WAVE; k.params = &u.w; k.items = u.w.items;
-    } else if (nhwc || half) {
-        k = LaunchPlan{};
-    } else if (plan_staged(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, u.s, k)) {
-        k.family = EVAM_KERNEL_STAGED; k.params = &u.s; k.items = u.s.items;
-    } else {
-        plan_rows(f, g, DW, DH, count, out_dtype, n_cu, xt, yt, x0_mask, kn, u.r, k);
-        k.family = EVAM_KERNEL_ROWS; k.params = &u.r; k.items = u.r.items;
-    }
-    return k;
-}
-
-// ROI-kernel plan for one format group with per-item geometry: the tile height, the LDS carve and the
-// staging buffer size, sized for the widest crop of the group (max_row_bytes = row_bytes_bound of it).
-// Returns false when the group needs the generic kernel (outputs wider than kRoiK x 256 pixels, taller
-// than 65535 rows, or a crop so wide that one output row's segments overflow the LDS budget).
-// The staging buffers are sized so that the whole grid fits on the chip in one round when it can: a ROI
-// batch is about one workgroup per CU slot (C3: 1,600 ROIs), and a second round starts its workgroups
-// only when first-round ones finish, paying record, geometry and setup latency again at the tail
-// (C3 with 6 instead of 7 resident per CU: the 64 smallest ROIs started at ~32 us and ended the launch,
-// profiles/r02r_c3_roi_timeline_before.json). Occupancy is capped by the kernel's registers
-// (kRoiWavesPerSimd); the buffers take what that occupancy leaves of the LDS (allocated in 1 KB
-// granules, checked against the runtime's occupancy calculator), between the widest crop's row and
-// 12 KB (EVAM_PP_ROI_BUF fixes it). `slots`: workgroups resident at once with that carve.
-constexpr int kRoiWavesPerSimd = 7;  // evam_pp_roi<*, *, 1> at kRoiK = 6: <= 72 VGPRs
-bool plan_roi(int f, int DW, int DH, int out_dtype, int px, int max_row_bytes, int count, int n_cu, const Knobs& kn,
-              QParams& q, int& base_tiles, int& lds, int64_t& slots, const void*& fn, bool dev = false) {
-    if (DW > kRoiK * kThreads || DH > 65535) return false;
-    q.DW = DW; q.DH = DH;
-    q.TH = (int64_t)DW * DH <= 32768 ? DH : std::max(8, std::min(DH, 16384 / DW));
-    if (kn.roi_th > 0) q.TH = std::max(1, std::min(DH, kn.roi_th));
-    base_tiles = (DH + q.TH - 1) / q.TH;
-    q.offXT = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0;
-    q.offYT = q.offXT + (int)sizeof(XTab) * DW;
-    q.offBuf = q.offYT + (int)sizeof(YTab) * q.TH;
-    const int64_t grid = (int64_t)count * base_tiles;
-    const int per_cu = (int)std::max<int64_t>(1, std::min<int64_t>(kRoiWavesPerSimd, (grid + n_cu - 1) / n_cu));
-    const int pxv = roi_px(px, DW, dev);
-    const uint32_t qw = (uint32_t)(DW / pxv);
-    q.mqw = qw > 1 ? (uint32_t)((0x100000000ull + qw - 1) / qw) : 0u;
-    const int nb = 2;
-    int buf = kn.roi_buf;
-    if (buf <= 0) buf = std::min(12 * 1024, ((((160 * 1024) / per_cu) & ~1023) - q.offBuf) / nb & ~15);
-    q.buf_bytes = (std::max(buf, max_row_bytes) + 15) & ~15;
-    lds = q.offBuf + nb * q.buf_bytes;
-    if (q.buf_bytes > 32 * 1024 || lds > 160 * 1024) return false;
-    fn = roi_kernel(f, out_dtype, pxv, dev);
-    int res = resident_per_cu(fn, lds);
-    while (kn.roi_buf <= 0 && res < per_cu && q.buf_bytes - 512 >= max_row_bytes) {
-        q.buf_bytes -= 512;
-        lds -= 512 * nb;
-        res = resident_per_cu(fn, lds);
-    }
-    slots = (int64_t)n_cu * res;
-    return true;
-}
 
 // HIP backend of the descriptor rings (evam_rings.h): events, streams, pinned and device memory. Every
 // failure is reported through fail() with the HIP error string.
@@ -4678,8 +3882,9 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     // Uniform group f's plan (plan_uniform: the one kernel-choice cascade) on the host tables xt / yt.
     UniformParams up;  // not cleared here: a plan_* function clears the struct it fills
     auto plan_group = [&](int f, const XTab* xt, const YTab* yt, bool pair_ok) {
-        return plan_uniform(f, geo[rep[f]], DW, DH, count[f], cfg->out_dtype, h->n_cu, xt, yt, x0_mask[f], kn, pair_ok, nhwc,
-                            nhwc_wave_ok, h->sc_tparams, up);
+        const UniformGroup u{f, geo[rep[f]], DW, DH, count[f], cfg->out_dtype, h->n_cu, xt, yt, x0_mask[f], kn, pair_ok, nhwc,
+                             nhwc_wave_ok};
+        return plan_uniform(HipKernels{}, u, h->sc_tparams, up);
     };
     // Does a uniform-geometry kernel serve interleaved uniform group f? Decided here, ahead of the descriptor block, so
     // that only a group the generic kernel serves puts its items' descriptors (which change with every set of
@@ -4721,7 +3926,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         if (nhwc) path[f] = !half && uniform[f] && kn.rows && planned_uniform_ok(f) ? kPathUniform : kPathGeneric;
         else if (half && uniform[f] && kn.rows) path[f] = planned_uniform_ok(f) ? kPathUniform : kPathGeneric;
         else if (uniform[f] && kn.rows) path[f] = kPathUniform;
-        else if (kn.roi && plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_cw[f]), count[f], h->n_cu,
+        else if (kn.roi && plan_roi(HipKernels{}, f, DW, DH,cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_cw[f]), count[f], h->n_cu,
                                     kn, qp[f], qbase[f], qlds[f], qslots[f], qfn[f])) path[f] = kPathRoi;
         else path[f] = kPathGeneric;
         any_generic |= path[f] == kPathGeneric;
@@ -5311,8 +4516,8 @@ int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, cons
     int64_t slots = 0;
     const void* fn = nullptr;
     HIP_TRY(hipSetDevice(h->device));
-    if (!plan_roi(f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_w), cap, h->n_cu, kn, q, base, lds, slots, fn,
-                  true))
+    if (!plan_roi(HipKernels{}, f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_w), cap, h->n_cu, kn, q, base, lds,
+                  slots, fn, true))
         return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: %dx%d output from %d-wide sources is not planned by the ROI kernel", who, DW,
                     DH, max_w);
     const int64_t units = (int64_t)cap * base;

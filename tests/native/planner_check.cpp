@@ -1,7 +1,7 @@
 // planner_check.cpp — host-only checks of the planner arithmetic libevam_pp.so shares with its kernels
-// (edge-video-analytics-microservice_amd/csrc/evam_geom.h), built and run under AddressSanitizer +
-// UBSan by tests/test_native_asan.py, together with the C oracle (oracle/evam_oracle.c) exercised on
-// tightly allocated frames so any out-of-bounds read in it is caught too.
+// (edge-video-analytics-microservice_amd/csrc/evam_geom.h) and of the planner itself (csrc/evam_plan.h, on a fake
+// kernel backend), built and run under AddressSanitizer + UBSan by tests/test_native_asan.py, together with the C
+// oracle (oracle/evam_oracle.c) exercised on tightly allocated frames so any out-of-bounds read in it is caught too.
 //
 // TEST INFRASTRUCTURE ONLY: links the oracle as the checker of the geometry rules.
 //
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../edge-video-analytics-microservice_amd/csrc/evam_geom.h"
+#include "../../edge-video-analytics-microservice_amd/csrc/evam_plan.h"
 #include "../../edge-video-analytics-microservice_amd/csrc/evam_clip_simd.h"
 
 extern "C" {
@@ -491,7 +492,300 @@ static void check_roi_xcd_deal() {
     printf("ROI XCD deal: %d random unit lists, permutations, frames on their XCDs, LPT-balanced\n", cases);
 }
 
+// ---- the host planner (csrc/evam_plan.h) on a fake kernel backend ----
+// A lookup returns (const void*)(1 + index in the family's table) for a variant that is built and nullptr otherwise, so
+// a check reads the variant a plan chose back from fn. resident(): `res` where set, else the library's own fallback
+// for a failed occupancy query, 160 KB / lds in 1..8.
+struct FakeKernels {
+    int res = 0;
+    static const void* at(int index, bool built) { return index >= 0 && built ? (const void*)(intptr_t)(1 + index) : nullptr; }
+    static int index_of(const void* fn) { return (int)(intptr_t)fn - 1; }
+    const void* rows(int f, int dt) const { return at(RowsVariants::index(f, out_kind(dt)), true); }
+    const void* staged(int f, int dt, int R, int nsegx, int nbuf) const {
+        return at(StagedVariants::index(f, out_kind(dt), R, nsegx, nbuf), StagedVariants::built(R, nsegx, nbuf));
+    }
+    const void* wave(int f, int dt, int px, bool reuse, bool nhwc) const {
+        return at(WaveVariants::index(f, out_kind(dt), px, reuse, nhwc), WaveVariants::built(out_kind(dt), px, nhwc));
+    }
+    const void* strip(int f, int dt, int px, int pr, bool nhwc) const {
+        return at(StripVariants::index(f, out_kind(dt), px, pr, nhwc), StripVariants::built(out_kind(dt), nhwc));
+    }
+    const void* band(int f, int dt, int px, bool dd, bool nhwc) const {
+        return at(BandVariants::index(f, out_kind(dt), px, dd, nhwc), BandVariants::built(out_kind(dt), px, dd, nhwc));
+    }
+    const void* roi(int f, int dt, int px, bool dev) const {
+        return at(RoiVariants::index(f, out_kind(dt), px, dev), RoiVariants::built(px, dev));
+    }
+    int resident(const void*, int lds) const { return res ? res : std::max(1, std::min(8, (160 * 1024) / std::max(lds, 1))); }
+};
+
+static bool same_plan(const LaunchPlan& a, const LaunchPlan& b) {
+    return a.family == b.family && a.fn == b.fn && a.block == b.block && a.lds == b.lds && a.gx == b.gx && a.gy == b.gy &&
+           a.tiles_per_item == b.tiles_per_item && a.params == b.params && a.items == b.items;
+}
+
+// One uniform group: geometry from roi_geometry, host tables, and a plan asked twice into the same structs, as
+// evam_pp_run asks (ahead of the descriptor block and at the launch). Returns the second plan.
+struct PlannedGroup {
+    Geom g{};
+    std::vector<XTab> xt;
+    std::vector<YTab> yt;
+    TParams t;
+    UniformParams up;
+    PlannedGroup() { memset(&t, 0, sizeof(t)); memset(&up, 0, sizeof(up)); }
+    LaunchPlan plan(const FakeKernels& be, int f, int DW, int DH, int count, int out_dtype, int n_cu, uint32_t x0_mask,
+                    const Knobs& kn, bool pair_ok, bool nhwc, bool nhwc_wave_ok) {
+        xt.resize(DW); yt.resize(DH);
+        build_tables_into(g, DW, DH, xt.data(), yt.data());
+        const UniformGroup u{f, g, DW, DH, count, out_dtype, n_cu, xt.data(), yt.data(), x0_mask, kn, pair_ok, nhwc, nhwc_wave_ok};
+        const LaunchPlan k0 = plan_uniform(be, u, t, up);
+        const TParams t0 = t;
+        const UniformParams up0 = up;
+        const LaunchPlan k1 = plan_uniform(be, u, t, up);
+        CHECK(same_plan(k0, k1) && memcmp(&t0, &t, sizeof(t)) == 0 && memcmp(&up0, &up, sizeof(up)) == 0,
+              "plan did not repeat: f=%d %dx%d count %d dtype %d", f, DW, DH, count, out_dtype);
+        return k1;
+    }
+};
+
+// Every bound the kernels rely on and only the planner keeps, over random uniform groups: all formats, dtypes and
+// layouts, tiny and odd outputs, every resize mode and placement, one and many crop-origin residues, default knobs and
+// each forcing knob, 1..8 resident workgroups per CU.
+static void check_plans() {
+    const int kCases = 20000;
+    int fam[7] = {0, 0, 0, 0, 0, 0, 0};  // none, rows, staged, wave, strip, band
+    PlannedGroup pg;
+    for (int it = 0; it < kCases; it++) {
+        const int f = uni(0, 3), bpp = fmt_bpp(f);
+        const bool yuv = f == kNV12 || f == kI420;
+        int W = uni(2, 4096), H = uni(2, 2304);
+        if (yuv) { W &= ~1; H &= ~1; }
+        const bool has = uni(0, 2) != 0;
+        const int rw = uni(2, W), rh = uni(2, H), rx = uni(0, W - rw), ry = uni(0, H - rh);
+        static const int kDW[] = {72, 224, 512, 640, 2048}, kNcu[] = {1, 8, 256};
+        const int cw_ = uni(0, 3), ch_ = uni(0, 2);
+        const int DW = cw_ == 0 ? uni(1, 64) : (cw_ == 1 ? 4 * uni(1, 512) : (cw_ == 2 ? uni(1, 2048) : kDW[uni(0, 4)]));
+        const int DH = ch_ == 0 ? uni(1, 3) : (ch_ == 1 ? uni(1, 2048) : uni(4, 640));
+        const int mode = uni(0, 2), placement = uni(0, 1);
+        if (roi_geometry(f, W, H, has, rx, ry, rw, rh, mode, placement, DW, DH, pg.g)) { it--; continue; }
+        const Geom& g = pg.g;
+        uint32_t x0_mask = 1u << (g.x0 & 31);
+        if (uni(0, 1))
+            for (int k = uni(1, 6); k > 0; k--) x0_mask |= 1u << (uni(0, 31) & (yuv ? ~1 : ~0));
+        const int count = uni(1, 150), n_cu = kNcu[uni(0, 2)], out_dtype = uni(0, 3);
+        // (interleaved 16-bit output is the generic kernel's: evam_pp_run never asks the planner for it)
+        const bool nhwc = out_kind(out_dtype) != 2 && uni(0, 3) == 0, nhwc_wave_ok = DW % 4 == 0 && uni(0, 1), pair_ok = uni(0, 1) != 0;
+        Knobs kn;
+        switch (uni(0, 9)) {
+        case 3: kn.strip = 2; break;
+        case 4: kn.band = 2; break;
+        case 5: kn.wave = 2; break;
+        case 6: kn.strip_px = uni(1, 2); break;
+        case 7: kn.band_px = 1 << uni(0, 2); break;
+        case 8: kn.strip_th = uni(1, 80); break;
+        case 9: kn.strip_nw = uni(1, 9); break;
+        default: break;
+        }
+        FakeKernels be;
+        be.res = uni(1, 8);
+        const LaunchPlan k = pg.plan(be, f, DW, DH, count, out_dtype, n_cu, x0_mask, kn, pair_ok, nhwc, nhwc_wave_ok);
+        const int lut16 = out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 16, per_launch = std::min(count, kArgItems);
+        const int idx = FakeKernels::index_of(k.fn);
+#define PCHECK(cond) CHECK(cond, "case %d family %u: f=%d crop %dx%d -> %dx%d in %dx%d count %d n_cu %d dtype %d nhwc %d res %d", \
+                           it, k.family, f, g.cw, g.ch, g.rw, g.rh, DW, DH, count, n_cu, out_dtype, (int)nhwc, be.res)
+        if (!k.family) { fam[0]++; PCHECK(nhwc || out_kind(out_dtype) == 2); continue; }
+        PCHECK(k.fn != nullptr && k.tiles_per_item > 0);
+        if (!k.fn) continue;
+        if (k.family == EVAM_KERNEL_STRIP) {
+            fam[4]++;
+            const TParams& p = pg.t;
+            const int px = ((idx >> 2) & 1) + 1, pr = (idx >> 1) & 1, nstrips = (DW + 64 * px - 1) / (64 * px);
+            PCHECK(p.nw >= 1 && p.nw <= 8 && k.block == 64 * p.nw && k.block <= 512 && p.TH >= 1 && p.TH <= 64);
+            PCHECK((p.tiles_x - 1) * 8 + p.nw <= kSfoot && p.tiles_x * p.nw >= nstrips && nstrips <= kMaxStrips);
+            PCHECK(k.gx == p.tiles_x && k.gy * p.TH >= DH && (k.gy - 1) * p.TH < DH && k.tiles_per_item == k.gx * k.gy);
+            PCHECK((int64_t)per_launch * k.tiles_per_item <= INT32_MAX);
+            PCHECK(k.lds + lut16 <= 64 * 1024 && k.lds == p.nw * p.wave_bytes + 16);
+            const int npc = f == kI420 ? 2 : (f == kBGRX ? 0 : 1);
+            PCHECK(p.wave_bytes == kStripD * (pr ? (npc ? 2048 : 1024) : (2 + 2 * npc) * strip_slot(f, px)));
+            PCHECK(p.DW == DW && p.DH == DH && p.cw == g.cw && p.rw == g.rw && p.ox == g.ox);
+            for (int e = 0; e < kSfoot; e++) {
+                const ColSpan s = p.sfoot[e];
+                if (s.x == -1 && s.y == -1) continue;
+                PCHECK(s.x >= 0 && s.x <= s.y && s.y <= g.cw - 1);
+                for (int r = 0; r < 32; r++) {
+                    if (!((x0_mask >> r) & 1u)) continue;
+                    int fsY, nY, fsC, nC;
+                    footprint_chunks(f, bpp, r + s.x, r + s.y, fsY, nY, fsC, nC);
+                    PCHECK(16 * nY <= strip_slot(f, px) && 16 * nC <= strip_slot(f, px));
+                    if (pr) PCHECK(16 * nY <= 512 && 16 * nC <= (f == kI420 ? 256 : 512));
+                }
+            }
+        } else if (k.family == EVAM_KERNEL_BAND) {
+            fam[5]++;
+            const TParams& p = pg.t;
+            const int px = 1 << ((idx >> 2) % 3);
+            PCHECK(k.block == 64 * p.nw && k.block <= 256 && p.nrY >= 1 && p.nrY <= 64 && p.TH >= 1 && p.TH <= 64);
+            PCHECK(k.lds + lut16 <= 64 * 1024 && k.lds == p.nw * p.wave_bytes + 16);
+            PCHECK(p.segY > 0 && p.segY % 16 == 0 && p.segC > 0 && p.segC % 16 == 0 && p.segY <= 1024);
+            PCHECK(p.wave_bytes == p.nrY * p.segY + (p.nrY / 2 + 1) * p.segC);
+            PCHECK(DW % px == 0 && p.nstrips == (DW + 64 * px - 1) / (64 * px) && p.nstrips <= kMaxStrips);
+            PCHECK((p.tiles_x - 1) * 8 + p.nw <= kSfoot && p.tiles_x * p.nw >= p.nstrips && k.gx == p.tiles_x);
+            // units (evam_pp_run: items x tiles_per_item) are the (band, strip) pairs: never more than the grid's waves
+            PCHECK(k.gy * p.TH >= DH && (k.gy - 1) * p.TH < DH && k.tiles_per_item == p.nstrips * k.gy);
+            PCHECK((int64_t)per_launch * k.tiles_per_item <= INT32_MAX);
+            for (int e = 0; e < kSfoot; e++) {
+                const ColSpan s = p.sfoot[e];
+                PCHECK((s.x == -1 && s.y == -1) || (s.x >= 0 && s.x <= s.y && s.y <= g.cw - 1));
+            }
+        } else if (k.family == EVAM_KERNEL_WAVE) {
+            fam[3]++;
+            const WParams& w = pg.up.w;
+            const int px = 1 << ((idx >> 2) % 3), npc = f == kI420 ? 2 : (f == kNV12 ? 1 : 0);
+            PCHECK(k.block == kThreads && w.TH >= 1 && w.TH <= 256 && k.gy == 0);
+            PCHECK(k.lds <= 64 * 1024 && (nhwc || kn.px || k.lds <= kn.wave_lds));
+            PCHECK(w.segY % 16 == 0 && w.segC % 16 == 0 && w.wave_bytes == 2 * (2 * w.segY + 2 * npc * w.segC));
+            PCHECK(k.lds == w.offBuf + 4 * w.wave_bytes && w.offBuf == (out_dtype != EVAM_DTYPE_U8 ? kLutBytes : 0));
+            PCHECK(DW % px == 0 && w.tiles_x * 64 * px >= DW);
+            PCHECK(k.tiles_per_item == w.tiles_x * ((DH + w.TH - 1) / w.TH) && (int64_t)count * k.tiles_per_item <= INT32_MAX);
+        } else if (k.family == EVAM_KERNEL_STAGED) {
+            fam[2]++;
+            const SParams& s = pg.up.s;
+            const int R = (idx / 3) % 2 + 1, nsegx = 1 << (idx % 3);
+            PCHECK(k.block == kThreads && s.TH >= 1 && s.TH <= 64 && s.TH % R == 0 && k.gy == 0);
+            PCHECK(s.slot_bytes > 0 && s.slot_bytes <= kSlot && s.slot_bytes % 16 == 0 && s.ntcol >= 0 && s.ntcol <= kTCols);
+            PCHECK(k.lds <= 160 * 1024 && k.lds == s.offBuf + 2 * s.buf_bytes);
+            PCHECK(s.tiles_x * 64 * nsegx >= DW && k.tiles_per_item == s.tiles_x * ((DH + s.TH - 1) / s.TH));
+            for (int c = 0; c < s.ntcol; c++)
+                PCHECK((s.tcol[c].x == -1 && s.tcol[c].y == -1) ||
+                       (s.tcol[c].x >= 0 && s.tcol[c].x <= s.tcol[c].y && s.tcol[c].y <= g.cw - 1));
+        } else {
+            fam[1]++;
+            const RParams& r = pg.up.r;
+            PCHECK(k.family == EVAM_KERNEL_ROWS && k.block == kThreads && k.gy == 0);
+            PCHECK((r.TW == 64 || r.TW == 128 || r.TW == 256 || r.TW == 512) && r.nsegx == r.TW / 64 && r.TH >= 1);
+            PCHECK(r.tiles_x * r.TW >= DW && k.tiles_per_item == r.tiles_x * ((DH + r.TH - 1) / r.TH));
+        }
+#undef PCHECK
+    }
+    for (int i = 1; i <= 5; i++) CHECK(fam[i] > 0, "the generator never reached family slot %d", i);
+    // the ROI plan: the LDS carve and the staging buffers, host lists and device lists
+    int roi_ok = 0;
+    for (int it = 0; it < kCases; it++) {
+        const int f = uni(0, 3), DW = uni(0, 3) ? uni(1, 640) : uni(1, 1800), DH = uni(0, 3) ? uni(1, 640) : uni(1, 70000);
+        const int out_dtype = uni(0, 3), px = 1 << uni(0, 2), count = uni(1, 4000), n_cu = uni(0, 2) ? 256 : uni(1, 300);
+        const int max_row_bytes = row_bytes_bound(f, uni(1, 4096));
+        const bool dev = uni(0, 2) == 0;
+        Knobs kn;
+        if (uni(0, 5) == 0) kn.roi_th = uni(1, 100);
+        if (uni(0, 5) == 0) kn.roi_buf = 512 * uni(1, 40);
+        FakeKernels be;
+        be.res = uni(0, 8);
+        QParams q[2];
+        int base[2] = {0, 0}, lds[2] = {0, 0};
+        int64_t slots[2] = {0, 0};
+        const void* fn[2] = {nullptr, nullptr};
+        bool ok[2];
+        for (int r = 0; r < 2; r++) {
+            memset(&q[r], 0, sizeof(QParams));
+            ok[r] = plan_roi(be, f, DW, DH, out_dtype, px, max_row_bytes, count, n_cu, kn, q[r], base[r], lds[r], slots[r], fn[r], dev);
+        }
+        CHECK(ok[0] == ok[1] && (!ok[0] || (memcmp(&q[0], &q[1], sizeof(QParams)) == 0 && base[0] == base[1] &&
+              lds[0] == lds[1] && slots[0] == slots[1] && fn[0] == fn[1])), "ROI plan did not repeat (case %d)", it);
+        if (!ok[0]) { CHECK(DW > kRoiK * kThreads || DH > 65535 || max_row_bytes > 8 * 1024 || kn.roi_buf > 0, "ROI plan refused %dx%d, row %d B", DW, DH, max_row_bytes); continue; }
+        roi_ok++;
+        const QParams& p = q[0];
+        const int pxv = roi_px(px, DW, dev);
+        const uint32_t qw = (uint32_t)(DW / pxv);
+#define QCHECK(cond) CHECK(cond, "ROI case %d: f=%d %dx%d dtype %d px %d count %d n_cu %d row %d B dev %d res %d", it, f, DW, DH, \
+                           out_dtype, px, count, n_cu, max_row_bytes, (int)dev, be.res)
+        QCHECK(fn[0] != nullptr && DW % pxv == 0);
+        QCHECK(p.buf_bytes >= max_row_bytes && p.buf_bytes % 16 == 0 && p.buf_bytes <= 32 * 1024);
+        QCHECK(lds[0] <= 160 * 1024 && lds[0] == p.offBuf + 2 * p.buf_bytes);
+        QCHECK(p.offYT == p.offXT + 16 * DW && p.offBuf == p.offYT + 16 * p.TH && p.TH >= 1 && p.TH <= DH);
+        QCHECK(base[0] == (DH + p.TH - 1) / p.TH);
+        QCHECK(p.mqw == (qw > 1 ? (uint32_t)((0x100000000ull + qw - 1) / qw) : 0u));
+        QCHECK(slots[0] == (int64_t)n_cu * be.resident(fn[0], lds[0]));
+#undef QCHECK
+    }
+    printf("plans: %d uniform groups (rows %d, staged %d, wave %d, strip %d, band %d, none %d) and %d ROI plans within the "
+           "kernels' bounds, each repeated byte for byte\n", kCases, fam[1], fam[2], fam[3], fam[4], fam[5], fam[0], roi_ok);
+}
+
+// The plans of the benchmark's workloads (bench.WORKLOADS: full frames, top-left placement, planar output, 256 CUs) at the
+// item counts it runs, each at a resident-workgroups figure below and above the planner's own target. The expected
+// values were printed by the planner as it stood before it moved into evam_plan.h; a change of any of them is a change
+// of a measured configuration.
+static void check_pinned_plans() {
+    struct Row {
+        const char* name;
+        int f, W, H, DW, DH, dtype, mode, frames, res;
+        uint32_t family;
+        int block, lds, gx, gy, tiles_per_item, TH, nw, wave_bytes;  // nw: 0 for the wave kernel's fixed four
+    };
+    const int U8 = EVAM_DTYPE_U8, F32 = EVAM_DTYPE_F32, NOA = EVAM_RESIZE_NO_ASPECT, ASP = EVAM_RESIZE_ASPECT, CROP = EVAM_RESIZE_ASPECT_CROP;
+    const uint32_t STRIP = EVAM_KERNEL_STRIP, BAND = EVAM_KERNEL_BAND, WAVE = EVAM_KERNEL_WAVE;
+    const Row rows[] = {
+        {"c1", kNV12, 768, 432, 512, 512, U8, NOA, 32, 2, BAND, 128, 10000, 1, 64, 128, 8, 2, 4992},
+        {"c1", kNV12, 768, 432, 512, 512, U8, NOA, 32, 8, BAND, 128, 10000, 1, 64, 128, 8, 2, 4992},
+        {"c1_b1", kNV12, 768, 432, 512, 512, U8, NOA, 1, 2, WAVE, 256, 12288, 0, 0, 128, 8, 0, 3072},
+        {"c1_b1", kNV12, 768, 432, 512, 512, U8, NOA, 1, 8, WAVE, 256, 12288, 0, 0, 128, 8, 0, 3072},
+        {"c1_i420", kI420, 768, 432, 512, 512, U8, NOA, 32, 2, BAND, 128, 10000, 1, 64, 128, 8, 2, 4992},
+        {"c1_i420", kI420, 768, 432, 512, 512, U8, NOA, 32, 8, BAND, 128, 10000, 1, 64, 128, 8, 2, 4992},
+        {"c2", kNV12, 1920, 1080, 512, 512, F32, NOA, 32, 2, STRIP, 256, 16400, 1, 16, 16, 32, 4, 4096},
+        {"c2", kNV12, 1920, 1080, 512, 512, F32, NOA, 32, 8, STRIP, 256, 16400, 1, 32, 32, 16, 4, 4096},
+        {"c2_i420", kI420, 1920, 1080, 512, 512, F32, NOA, 32, 2, STRIP, 256, 16400, 1, 16, 16, 32, 4, 4096},
+        {"c2_i420", kI420, 1920, 1080, 512, 512, F32, NOA, 32, 8, STRIP, 256, 16400, 1, 32, 32, 16, 4, 4096},
+        {"c4 x64", kNV12, 3840, 2160, 640, 640, F32, ASP, 64, 2, STRIP, 320, 40976, 1, 10, 10, 64, 5, 8192},
+        {"c4 x64", kNV12, 3840, 2160, 640, 640, F32, ASP, 64, 8, STRIP, 320, 40976, 1, 12, 12, 54, 5, 8192},
+        {"c4 x32", kNV12, 3840, 2160, 640, 640, F32, ASP, 32, 2, STRIP, 320, 40976, 1, 16, 16, 40, 5, 8192},
+        {"c4 x32", kNV12, 3840, 2160, 640, 640, F32, ASP, 32, 8, STRIP, 320, 40976, 1, 24, 24, 27, 5, 8192},
+        {"c4 x16", kNV12, 3840, 2160, 640, 640, F32, ASP, 16, 2, STRIP, 320, 40976, 1, 32, 32, 20, 5, 8192},
+        {"c4 x16", kNV12, 3840, 2160, 640, 640, F32, ASP, 16, 8, STRIP, 320, 40976, 1, 46, 46, 14, 5, 8192},
+        {"c4 x8", kNV12, 3840, 2160, 640, 640, F32, ASP, 8, 2, STRIP, 320, 40976, 1, 64, 64, 10, 5, 8192},
+        {"c4 x8", kNV12, 3840, 2160, 640, 640, F32, ASP, 8, 8, STRIP, 320, 40976, 1, 92, 92, 7, 5, 8192},
+        {"c5", kNV12, 1920, 1080, 224, 224, F32, CROP, 32, 2, STRIP, 256, 16400, 1, 16, 16, 14, 4, 4096},
+        {"c5", kNV12, 1920, 1080, 224, 224, F32, CROP, 32, 8, STRIP, 256, 16400, 1, 32, 32, 7, 4, 4096},
+        {"c5_bgrx", kBGRX, 768, 432, 224, 224, F32, CROP, 32, 2, STRIP, 256, 8208, 1, 16, 16, 14, 4, 2048},
+        {"c5_bgrx", kBGRX, 768, 432, 224, 224, F32, CROP, 32, 8, STRIP, 256, 8208, 1, 32, 32, 7, 4, 2048},
+    };
+    PlannedGroup pg;
+    for (const Row& r : rows) {
+        CHECK(roi_geometry(r.f, r.W, r.H, false, 0, 0, 0, 0, r.mode, EVAM_PLACE_TOP_LEFT, r.DW, r.DH, pg.g) == 0, "%s geometry", r.name);
+        FakeKernels be;
+        be.res = r.res;
+        const LaunchPlan k = pg.plan(be, r.f, r.DW, r.DH, r.frames, r.dtype, 256, 1u << (pg.g.x0 & 31), Knobs{}, true, false, false);
+        const bool wave = k.family == EVAM_KERNEL_WAVE;
+        const int TH = wave ? pg.up.w.TH : pg.t.TH, nw = wave ? 0 : pg.t.nw, wb = wave ? pg.up.w.wave_bytes : pg.t.wave_bytes;
+        CHECK(k.family == r.family, "%s res %d: family %u", r.name, r.res, k.family);
+        CHECK(k.block == r.block && k.lds == r.lds, "%s res %d: block %d lds %d", r.name, r.res, k.block, k.lds);
+        CHECK(k.gx == r.gx && k.gy == r.gy && k.tiles_per_item == r.tiles_per_item, "%s res %d: grid %d x %d, %d per item", r.name,
+              r.res, k.gx, k.gy, k.tiles_per_item);
+        CHECK(TH == r.TH && nw == r.nw && wb == r.wave_bytes, "%s res %d: TH %d nw %d wave_bytes %d", r.name, r.res, TH, nw, wb);
+    }
+    // c3: 1,600 ROIs of up to 400 source columns -> 72 x 72 fp32, two pixels per lane
+    struct RoiRow { int res, lds, buf_bytes; int64_t slots; };
+    const RoiRow rrows[] = {{6, 9216, 1920, 1536}, {7, 22528, 8576, 1792}};
+    for (const RoiRow& r : rrows) {
+        FakeKernels be;
+        be.res = r.res;
+        QParams q;
+        memset(&q, 0, sizeof(q));
+        int base = 0, lds = 0;
+        int64_t slots = 0;
+        const void* fn = nullptr;
+        CHECK(plan_roi(be, kNV12, 72, 72, F32, 2, row_bytes_bound(kNV12, 400), 1600, 256, Knobs{}, q, base, lds, slots, fn), "c3 ROI plan");
+        CHECK(fn != nullptr && base == 1 && q.TH == 72 && q.offXT == 3072 && q.offYT == 4224 && q.offBuf == 5376 && q.mqw == 119304648u,
+              "c3 res %d: carve %d %d %d %d mqw %u", r.res, q.TH, q.offXT, q.offYT, q.offBuf, q.mqw);
+        CHECK(lds == r.lds && q.buf_bytes == r.buf_bytes && slots == r.slots, "c3 res %d: lds %d buf %d slots %lld", r.res, lds,
+              q.buf_bytes, (long long)slots);
+    }
+    printf("pinned plans: %d benchmark rows and %d ROI rows as the planner gave them before the split\n",
+           (int)(sizeof(rows) / sizeof(rows[0])), (int)(sizeof(rrows) / sizeof(rrows[0])));
+}
+
 int main() {
+    check_plans();
+    check_pinned_plans();
     check_six_columns();
     check_clip_simd();
     check_roi_tail();

@@ -1,10 +1,12 @@
 """The plans the default planner picks as item counts and crop widths grow, bit-exact vs the C oracle.
 
-The host planner (plan_strip / plan_band / plan_roi in csrc/evam_pp.hip) turns a call's item count, output size and
-widest crop into a tile height, a wave count, an LDS carve and sometimes another kernel family. It asks the HIP
-occupancy calculator, so it cannot be unit-tested on the CPU, and ``evam_pp_stats.kernels`` reports only the family:
-these tests make the planner produce each plan by issuing the call a real batch would issue, with no EVAM_PP_* knob
-set, and compare every output element with the oracle.
+The host planner (plan_strip / plan_band / plan_roi in csrc/evam_plan.h) turns a call's item count, output size and
+widest crop into a tile height, a wave count, an LDS carve and sometimes another kernel family. That a plan is
+well-formed (every bound its kernel relies on) and what the benchmark's plans are is checked on the CPU, on a fake
+kernel backend (tests/native/planner_check.cpp: check_plans, check_pinned_plans; tests/test_native_asan.py). What only
+the GPU shows is that the kernels compute bit-exact output under each plan, and ``evam_pp_stats.kernels`` reports only
+the family: these tests make the planner produce each plan by issuing the call a real batch would issue, with no
+EVAM_PP_* knob set, and compare every output element with the oracle.
 
 A plan depends on the format, the geometry, the output dtype, the item count, the CU count, the crop origins and
 (I420) the plane distance, not on whether the items are distinct frames. So a launch of n items repeats K = 2 or 3

@@ -2,7 +2,8 @@
 
 Builds tests/native/planner_check.cpp — the planner arithmetic libevam_pp.so shares with its kernels
 (csrc/evam_geom.h: ROI clipping and geometry, OpenCV coefficient entries, staged footprints, LDS
-staging bounds, algorithmic bytes, ROI launch order) — together with the C oracle, both with
+staging bounds, algorithmic bytes, ROI launch order; csrc/evam_plan.h: the planner on a fake kernel backend, every
+bound its kernels rely on over random groups, and the benchmark workloads' plans pinned) — together with the C oracle, both with
 ``-fsanitize=address,undefined -fno-sanitize-recover=all``, and runs it. The checks compare the
 planner with the oracle's geometry over random and extreme (int32-overflowing) rects, check every
 staging bound it computes against brute force, and drive the oracle on exactly-sized frame
@@ -35,6 +36,7 @@ def test_planner_and_oracle_under_asan_ubsan(tmp_path):
     print(r.stdout)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
     assert "all checks passed" in r.stdout
+    assert "plans: 20000 uniform groups" in r.stdout and "pinned plans: 22 benchmark rows and 2 ROI rows" in r.stdout
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
