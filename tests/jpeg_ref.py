@@ -1,6 +1,9 @@
 """numpy restatement of libjpeg's baseline encoder as cv2.imencode('.jpg') and Pillow (subsampling=2) drive it:
 baseline, 4:2:0, JDCT_ISLOW, Annex K tables, no restart interval. ``encode`` returns the whole JFIF file and a few
-counts of what the entropy coder met, so a test can assert that its input really exercised the hard parts.
+counts of what the entropy coder met, so a test can assert that its input really exercised the hard parts. Its
+``sampling`` and ``restart`` arguments write the other files the decoder accepts, as Pillow's ``subsampling=0 / 1``,
+mode ``L`` and ``restart_marker_blocks`` make libjpeg write them: 4:2:2 (h2v1 down-sampling, 16x8 MCUs), 4:4:4, one
+grey component, and restart intervals (a DRI segment, RST0..7 in turn behind bits padded with ones).
 
 The colour conversion, down-sampling, DCT and quantisation are vectorised over blocks; only the entropy loop runs per
 block. ``tests/test_jpeg_host.py`` pins this file byte for byte to files libjpeg-turbo (through Pillow) wrote."""
@@ -77,20 +80,30 @@ def quant_tables(quality: int):
     return tuple(np.clip((base * scale + 50) // 100, 1, 255).astype(np.int64) for base in (Q_LUMA, Q_CHROMA))
 
 
-def header(width: int, height: int, quality: int) -> bytes:
+SAMPLINGS = {"420": (2, 2), "422": (2, 1), "444": (1, 1), "grey": (1, 1)}
+
+
+def header(width: int, height: int, quality: int, sampling: str = "420", restart: int = 0) -> bytes:
+    """Everything up to the scan, as libjpeg writes it: grey files carry the luma tables alone, and a DRI segment
+    stands between the last DHT and the SOS."""
     ql, qc = quant_tables(quality)
+    hs, vs = SAMPLINGS[sampling]
+    ncomp = 1 if sampling == "grey" else 3
     b = bytearray(b"\xFF\xD8")
     b += b"\xFF\xE0\x00\x10JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00"
-    for i, t in enumerate((ql, qc)):
+    for i, t in enumerate((ql, qc)[:2 if ncomp == 3 else 1]):
         b += b"\xFF\xDB\x00\x43" + bytes([i]) + bytes(int(v) for v in t[ZIGZAG])
-    b += b"\xFF\xC0\x00\x11\x08" + bytes([height >> 8, height & 255, width >> 8, width & 255])
-    b += b"\x03\x01\x22\x00\x02\x11\x01\x03\x11\x01"
+    b += bytes([0xFF, 0xC0, 0x00, 8 + 3 * ncomp, 0x08, height >> 8, height & 255, width >> 8, width & 255, ncomp])
+    b += bytes([0x01, hs << 4 | vs, 0x00]) + (b"\x02\x11\x01\x03\x11\x01" if ncomp == 3 else b"")
     for tc_th, bits, vals in ((0x00, DC_LUMA_BITS, DC_VALS), (0x10, AC_LUMA_BITS, AC_LUMA_VALS),
-                              (0x01, DC_CHROMA_BITS, DC_VALS), (0x11, AC_CHROMA_BITS, AC_CHROMA_VALS)):
+                              (0x01, DC_CHROMA_BITS, DC_VALS), (0x11, AC_CHROMA_BITS, AC_CHROMA_VALS))[:4 if ncomp == 3 else 2]:
         n = 2 + 1 + 16 + len(vals)
         b += b"\xFF\xC4" + bytes([n >> 8, n & 255, tc_th]) + bytes(bits) + bytes(vals)
-    b += b"\xFF\xDA\x00\x0C\x03\x01\x00\x02\x11\x03\x11\x00\x3F\x00"
-    assert len(b) == HEADER_LEN
+    if restart:
+        b += bytes([0xFF, 0xDD, 0x00, 0x04, restart >> 8, restart & 255])
+    b += bytes([0xFF, 0xDA, 0x00, 6 + 2 * ncomp, ncomp, 0x01, 0x00]) + (b"\x02\x11\x03\x11" if ncomp == 3 else b"")
+    b += b"\x00\x3F\x00"
+    assert sampling != "420" or restart or len(b) == HEADER_LEN
     return bytes(b)
 
 
@@ -118,6 +131,13 @@ def _downsample(c, h16):
     bias = np.tile(np.array([1, 2]), w // 4 + 1)[:w // 2]
     d = (c[0::2, 0::2] + c[0::2, 1::2] + c[1::2, 0::2] + c[1::2, 1::2] + bias) >> 2
     return _pad(d, h16 // 2, w // 2)
+
+
+def _downsample_h2v1(c, h8):
+    """h2v1_downsample (bias 0, 1, 0, 1) on a plane already padded to a multiple of 16 columns."""
+    h, w = c.shape
+    bias = np.tile(np.array([0, 1]), w // 4 + 1)[:w // 2]
+    return _pad((c[:, 0::2] + c[:, 1::2] + bias) >> 1, h8, w // 2)
 
 
 _C = {k: int(v * 8192 + 0.5) for k, v in dict(
@@ -170,53 +190,92 @@ def blocks_quantised(plane: np.ndarray, qtab: np.ndarray) -> np.ndarray:
     return q[..., ZIGZAG]
 
 
-def coefficients(bgr: np.ndarray, quality: int):
-    """The MCU-ordered blocks of the scan: ([n_mcu, 6, 64] int64, number of dummy Y blocks)."""
+def mcu_grid(w: int, h: int, sampling: str = "420"):
+    """(MCU rows, MCUs per row, blocks per MCU). A grey scan is not interleaved: its MCU is one block."""
+    hs, vs = SAMPLINGS[sampling]
+    return -(-h // (8 * vs)), -(-w // (8 * hs)), hs * vs + (0 if sampling == "grey" else 2)
+
+
+def coefficients(bgr: np.ndarray, quality: int, sampling: str = "420"):
+    """The MCU-ordered blocks of the scan: ([n_mcu, blocks per MCU, 64] int64, number of dummy Y blocks)."""
     h, w = bgr.shape[:2]
     ql, qc = quant_tables(quality)
+    hs, vs = SAMPLINGS[sampling]
+    mr, mc, bpm = mcu_grid(w, h, sampling)
+    h8, w8, hm, wm = -(-h // 8) * 8, -(-w // 8) * 8, mr * 8 * vs, mc * 8 * hs
+    if sampling == "grey":
+        return blocks_quantised(_pad(bgr[..., 1].astype(np.int64), h8, w8), ql).reshape(mr * mc, 1, 64), 0
     y, cb, cr = ycc(bgr)
-    h8, w8, h16, w16 = -(-h // 8) * 8, -(-w // 8) * 8, -(-h // 16) * 16, -(-w // 16) * 16
     yq = blocks_quantised(_pad(y, h8, w8), ql)
-    mr, mc = h16 // 16, w16 // 16
-    yb = np.zeros((mr * 2, mc * 2, 64), np.int64)
+    yb = np.zeros((mr * vs, mc * hs, 64), np.int64)
     yb[:h8 // 8, :w8 // 8] = yq
-    cbq = blocks_quantised(_downsample(_pad(cb, h, w16), h16), qc)
-    crq = blocks_quantised(_downsample(_pad(cr, h, w16), h16), qc)
-    out = np.zeros((mr, mc, 6, 64), np.int64)
+    out = np.zeros((mr, mc, bpm, 64), np.int64)
     dummies = 0
-    for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
-        out[:, :, k] = yb[dy::2, dx::2]
-        rows = (np.arange(mr) * 2 + dy) >= h8 // 8
-        cols = (np.arange(mc) * 2 + dx) >= w8 // 8
+    for k, (dy, dx) in enumerate((dy, dx) for dy in range(vs) for dx in range(hs)):
+        out[:, :, k] = yb[dy::vs, dx::hs]
+        rows = (np.arange(mr) * vs + dy) >= h8 // 8
+        cols = (np.arange(mc) * hs + dx) >= w8 // 8
         dummy = rows[:, None] | cols[None, :]
         if k:
             out[:, :, k, 0] = np.where(dummy, out[:, :, k - 1, 0], out[:, :, k, 0])
         dummies += int(dummy.sum())
-    out[:, :, 4] = cbq
-    out[:, :, 5] = crq
-    return out.reshape(mr * mc, 6, 64), dummies
+    for k, c in ((hs * vs, cb), (hs * vs + 1, cr)):
+        if sampling == "420":
+            c = _downsample(_pad(c, h, wm), hm)
+        elif sampling == "422":
+            c = _downsample_h2v1(_pad(c, h, wm), hm)
+        else:
+            c = _pad(c, hm, wm)
+        out[:, :, k] = blocks_quantised(c, qc)
+    return out.reshape(mr * mc, bpm, 64), dummies
+
+
+def _pack(codes, lens):
+    """(code, length) pairs -> (bytes padded with ones and stuffed, number of stuffed zeros)."""
+    codes = np.asarray(codes, np.int64)
+    lens = np.asarray(lens, np.int64)
+    total = int(lens.sum())
+    idx = np.repeat(np.arange(len(lens)), lens)
+    pos = np.arange(total) - np.repeat(np.cumsum(lens) - lens, lens)
+    bits = ((codes[idx] >> (lens[idx] - 1 - pos)) & 1).astype(np.uint8)
+    bits = np.concatenate([bits, np.ones((-total) % 8, np.uint8)])
+    raw = np.packbits(bits)
+    ff = raw == 0xFF
+    out = np.zeros(len(raw) + int(ff.sum()), np.uint8)
+    out[np.arange(len(raw)) + np.cumsum(ff) - ff] = raw
+    return out.tobytes(), int(ff.sum())
 
 
 def _category(v: int) -> int:
     return int(abs(v)).bit_length()
 
 
-def encode(bgr_u8: np.ndarray, quality: int):
-    """(JFIF bytes, stats) of an [H, W, 3] uint8 BGR image. stats: zrl, stuffed, max_category, dummy_blocks,
+def encode(bgr_u8: np.ndarray, quality: int, *, sampling: str = "420", restart: int = 0):
+    """(JFIF bytes, stats) of an [H, W, 3] uint8 BGR image. sampling: "420", "422", "444", or "grey" (one component,
+    the G channel). restart: MCUs per restart interval, 0 for none; the bits before each RSTn are padded with ones and
+    the DC predictions start again behind it. stats: zrl, stuffed, max_category, dummy_blocks,
     min_block_bits, max_dc_category (the largest DC-difference category), max_zrl_run (the most ZRL codes in front of
     one AC coefficient), no_eob_blocks (blocks whose coefficient 63 is non-zero: they end without an EOB)."""
     bgr = np.ascontiguousarray(bgr_u8)
     assert bgr.dtype == np.uint8 and bgr.ndim == 3 and bgr.shape[2] == 3
+    assert 0 <= restart <= 65535
     h, w = bgr.shape[:2]
-    coef, dummies = coefficients(bgr, quality)
-    codes, lens = [], []
+    coef, dummies = coefficients(bgr, quality, sampling)
+    bpm = coef.shape[1]
+    nluma = bpm if sampling == "grey" else bpm - 2
+    codes, lens, scan = [], [], bytearray()
     stats = {"zrl": 0, "stuffed": 0, "max_category": 0, "dummy_blocks": dummies, "min_block_bits": 1 << 30,
              "max_dc_category": 0, "max_zrl_run": 0, "no_eob_blocks": 0}
     pred = [0, 0, 0]
     flat = coef.reshape(-1, 64).tolist()
     for bi, blk in enumerate(flat):
-        k6 = bi % 6
-        comp = 0 if k6 < 4 else k6 - 3
+        kb = bi % bpm
+        if restart and kb == 0 and bi and (bi // bpm) % restart == 0:
+            data, stuffed = _pack(codes, lens)
+            scan += data + bytes([0xFF, 0xD0 + (bi // bpm // restart - 1) % 8])
+            stats["stuffed"] += stuffed
+            codes, lens, pred = [], [], [0, 0, 0]
+        comp = 0 if kb < nluma else kb - nluma + 1
         dc, ac = (HUFF["dc0"], HUFF["ac0"]) if comp == 0 else (HUFF["dc1"], HUFF["ac1"])
         n0 = len(lens)
         v = blk[0] - pred[comp]
@@ -258,16 +317,6 @@ def encode(bgr_u8: np.ndarray, quality: int):
         else:
             stats["no_eob_blocks"] += 1
         stats["min_block_bits"] = min(stats["min_block_bits"], sum(lens[n0:]))
-    codes = np.asarray(codes, np.int64)
-    lens = np.asarray(lens, np.int64)
-    total = int(lens.sum())
-    idx = np.repeat(np.arange(len(lens)), lens)
-    pos = np.arange(total) - np.repeat(np.cumsum(lens) - lens, lens)
-    bits = ((codes[idx] >> (lens[idx] - 1 - pos)) & 1).astype(np.uint8)
-    bits = np.concatenate([bits, np.ones((-total) % 8, np.uint8)])
-    raw = np.packbits(bits)
-    ff = raw == 0xFF
-    stats["stuffed"] = int(ff.sum())
-    out = np.zeros(len(raw) + stats["stuffed"], np.uint8)
-    out[np.arange(len(raw)) + np.cumsum(ff) - ff] = raw
-    return header(w, h, quality) + out.tobytes() + b"\xFF\xD9", stats
+    data, stuffed = _pack(codes, lens)
+    stats["stuffed"] += stuffed
+    return header(w, h, quality, sampling, restart) + bytes(scan) + data + b"\xFF\xD9", stats

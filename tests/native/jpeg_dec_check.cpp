@@ -6,8 +6,9 @@
 // Both must end with the same status and the same coefficients, inside exactly-sized heap buffers, within the round
 // bound. The same is asked with 64-bit sub-sequences in chunks of 4 (so that small files cross chunk borders) and of
 // 20,000 seeded random damaged scans derived from the good files.
-//   usage: jpeg_dec_check file... [--damaged file...] [--expect-bad file...]
+//   usage: jpeg_dec_check file... [--good-only file...] [--damaged file...] [--expect-bad file...]
 //   Files in front of the flags must decode with status 0 (or be refused by the parse) and seed the random scans;
+//   after --good-only they must decode with status 0 and seed nothing (files too long to damage 20,000 times);
 //   after --damaged any status is accepted, after --expect-bad only a non-zero one.
 #include <cstdint>
 #include <cstdio>
@@ -173,15 +174,16 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--damaged") { mode = 1; continue; }
         if (std::string(argv[i]) == "--expect-bad") { mode = 2; continue; }
+        if (std::string(argv[i]) == "--good-only") { mode = 3; continue; }
         const std::vector<uint8_t> file = read_file(argv[i]);
         int status = 0;
         n_files++;
         if (!check_file(file, argv[i], &status)) { n_refused++; printf("%s: refused (%d)\n", argv[i], status); continue; }
         printf("%s: status %d\n", argv[i], status);
         if (mode == 2) CHECK(status != 0, "%s: a damaged scan ended with status 0", argv[i]);
-        else if (mode == 0) {
+        else if (mode == 0 || mode == 3) {
             CHECK(status == 0, "%s: a good file ended with status %d", argv[i], status);
-            good.push_back(file);
+            if (mode == 0) good.push_back(file);
         }
     }
     int n_random = 0, n_random_bad = 0;

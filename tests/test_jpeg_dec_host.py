@@ -272,6 +272,80 @@ def test_blocks_longer_than_a_sub_sequence(evam, colour):
     assert min(np.diff([0] + ends)) > C.source_constant("kJdecSubBits")
     assert C.max_code_length(f) == 16
     check(evam.native, f, pillow_pixels(f), f"long blocks, colour {colour}")
+    if colour:
+        f, ends = C.long_block_file(40, 24, True, seed=3, sampling="422", restart=1)
+        assert evam.jpeg_info(f).restart_interval == 1 and evam.jpeg_info(f).h_samp == 2 and evam.jpeg_info(f).v_samp == 1
+        assert len(C.rst_markers(f)) == 3 * 3 - 1 and len(ends) == 9 * 4
+        check(evam.native, f, pillow_pixels(f), "long blocks, 4:2:2, restart 1")
+
+
+# ---- the files of tests/test_gpu_jpeg_dec_sweep.py: the host twin is what the GPU is compared with there ------------
+
+def check_files(N, files, what):
+    """Files of one geometry in one call of the twin, each against Pillow's decode of it."""
+    px, status, _ = decode(N, files)
+    assert status.tolist() == [0] * len(files), what
+    for i, f in enumerate(files):
+        ref = pillow_pixels(f)
+        bad = np.argwhere(px[i] != ref)
+        assert bad.size == 0, f"{what} file {i}: {len(bad)} bytes differ, first {bad[:3].tolist()}"
+
+
+@pytest.mark.parametrize("sampling,restart", [("444", 0), ("444", 1), ("422", 0), ("422", 1), ("grey", 0), ("grey", 1),
+                                              ("420", 1)])
+def test_sweep_residue_grids_equal_pillow(evam, sampling, restart):
+    """The whole residue grids of the GPU sweep (not a sample of them), the same files."""
+    pytest.importorskip("PIL")
+    widths, heights = C.RESIDUE_GRIDS[sampling]
+    n = 0
+    for h in heights:
+        for w, files in C.residue_files(sampling, restart, h, widths):
+            info = evam.jpeg_info(files[0])
+            assert (info.width, info.height, info.restart_interval) == (w, h, restart)
+            check_files(evam.native, files, f"{sampling} restart {restart} {w}x{h}")
+            n += 1
+    assert n == len(widths) * len(heights)
+
+
+@pytest.mark.parametrize("sampling", C.SAMPLINGS)
+def test_sweep_long_restart_scans_equal_pillow(evam, sampling):
+    """Scans longer than two passes of evam_jdec_unstuff: a marker behind every MCU (the cut-pairs file), and behind
+    every MCU row (the wide frame); and the tall frame."""
+    pytest.importorskip("PIL")
+    f = C.cut_pairs_file(sampling)
+    assert C.cut_pairs_properties(f)["len"] > 2 * C.PASS + 1 and evam.jpeg_info(f).restart_interval == 1
+    check_files(evam.native, [f], f"cut pairs {sampling}")
+    (what, wide), (_, tall) = C.wide_and_tall_files(sampling)
+    s, e = C.scan_bounds(wide)
+    assert e - s > 2 * C.PASS + 1 and evam.jpeg_info(wide).restart_interval == -(-C.WIDE // C.mcu_size(sampling)[0])
+    assert len(C.rst_markers(wide)) == -(-24 // C.mcu_size(sampling)[1]) - 1
+    check_files(evam.native, [wide], f"{what} {sampling}")
+    check_files(evam.native, [tall], f"24x1100 {sampling}")
+
+
+def test_sweep_long_and_many_intervals_equal_pillow(evam):
+    """The grey file with two intervals longer than S * T bits, and the files with 2,047, 292 and 255 markers."""
+    pytest.importorskip("PIL")
+    f, restart, mcus = C.long_interval_file("grey")
+    table = C.interval_table(f)
+    chunk = C.source_constant("kJdecSubBits") * C.source_constant("kJdecChunk") // 8
+    assert len(table) == 4 and table[1] > chunk and table[2] - table[1] > chunk and table[3] - table[2] < chunk
+    check_files(evam.native, [f], "long intervals")
+    for (what, f, restart), markers in zip(C.many_interval_files(), (2047, 292, 255)):
+        assert len(C.rst_markers(f)) == markers and evam.jpeg_info(f).restart_interval == restart
+        check_files(evam.native, [f], what)
+    for sampling in ("422", "444"):
+        for restart in (1, 3):
+            f, _ = C.long_block_file(40, 24, True, seed=restart, sampling=sampling, restart=restart)
+            check_files(evam.native, [f], f"long blocks {sampling} restart {restart}")
+
+
+def test_damaged_restart_scans_end_with_a_status(evam):
+    N = evam.native
+    for name, f, must_fail in C.damaged_restart_scans():
+        px, status, padding = decode(N, [f], N.FOURCC_BGRX, 16)
+        assert status[0] == N.ERR_INVALID_ARG and must_fail, name
+        assert (padding == 0xA5).all(), name
 
 
 # ---- pipeline server: the source item forms, with a stand-in decoder -----------------------------------------------

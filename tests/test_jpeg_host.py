@@ -104,6 +104,33 @@ def test_ref_equals_fresh_pillow():
         assert jpeg_ref.encode(img, q)[0] == buf.getvalue(), (w, h, q, kind)
 
 
+@pytest.mark.parametrize("sampling", ["420", "422", "444", "grey"])
+def test_ref_samplings_and_restarts_equal_fresh_pillow(sampling):
+    """Every file the decoder accepts that ``encode`` writes: each sampling x restart interval in {0, 1, 5, MCUs per
+    row} x three contents x qualities 10, 75, 100 x two odd sizes, the whole file equal to Pillow's (DRI included)."""
+    Image = pytest.importorskip("PIL.Image")
+    n = 0
+    for w, h in ((37, 23), (50, 33)):
+        per_row = jpeg_ref.mcu_grid(w, h, sampling)[1]
+        for restart in (0, 1, 5, per_row):
+            for kind in ("noise", "sat", "grad"):
+                for q in (10, 75, 100):
+                    img = content(kind, w, h, seed=n)
+                    buf = io.BytesIO()
+                    if sampling == "grey":
+                        im, args = Image.fromarray(np.ascontiguousarray(img[..., 1])), {}
+                    else:
+                        im = Image.fromarray(np.ascontiguousarray(img[..., ::-1]))
+                        args = {"subsampling": {"444": 0, "422": 1, "420": 2}[sampling]}
+                    im.save(buf, "JPEG", quality=q, restart_marker_blocks=restart, **args)
+                    got, _ = jpeg_ref.encode(img, q, sampling=sampling, restart=restart)
+                    assert got == buf.getvalue(), (w, h, restart, kind, q)
+                    assert (b"\xFF\xDD\x00\x04" in got[:700]) == (restart > 0)
+                    n += 1
+    assert n == 72
+    assert jpeg_ref.encode(img, 75)[0] == jpeg_ref.encode(img, 75, sampling="420", restart=0)[0]
+
+
 @pytest.mark.parametrize("name,img,q,ref", CASES, ids=[c[0] for c in CASES])
 def test_header_and_bound(evam, name, img, q, ref):
     h, w = img.shape[:2]

@@ -97,6 +97,25 @@ def test_three_hundred_fresh_pillow_files(evam):
     assert n >= 300 and 100 < with_rst < 250
 
 
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_sweep_restart_files_equal_pillow(evam, fmt):
+    """The 4:2:0 files tests/test_gpu_jpeg_dec_sweep.py decodes to planes: a marker behind every MCU (the cut-pairs
+    file's even-sized sibling and the 256-MCU gradient), and two intervals longer than one chunk of evam_jdec_sync."""
+    pytest.importorskip("PIL")
+    f = C.cut_pairs_file("420")
+    assert len(C.rst_markers(f)) == C.cut_pairs_width("420") // 16 - 1 and evam.jpeg_planes_ok(evam.jpeg_info(f))
+    check(evam.native, [f], [PC.pillow_planes(f)], fmt, ["unequal"], "cut pairs")
+    what, f, restart = C.many_interval_files()[2]
+    assert evam.jpeg_info(f).restart_interval == 1 and len(C.rst_markers(f)) == 255
+    check(evam.native, [f], [PC.pillow_planes(f)], fmt, ["window"], what)
+    f, restart, mcus = C.long_interval_file("420")
+    table = C.interval_table(f)
+    chunk = C.source_constant("kJdecSubBits") * C.source_constant("kJdecChunk") // 8
+    assert len(table) == 4 and table[1] > chunk and table[2] - table[1] > chunk > table[3] - table[2]
+    for kind in ("unequal", "window"):
+        check(evam.native, [f], [PC.pillow_planes(f)], fmt, [kind], "long intervals")
+
+
 # ---- refusals ------------------------------------------------------------------------------------------------------
 
 def refused(N, files, surface, want, words, **kw):
