@@ -95,7 +95,8 @@ inline void track_state_init(evam_track_state* s) {
     for (int t = 0; t < kTrackSlots; t++) s->slots[t].classified_at = EVAM_TRACK_NONE;
 }
 
-// One frame of one stream, sequentially. gate: run step 7 (n_set < 0: every label). ids: [n]; due: [n] or NULL.
+// One frame of one stream, sequentially. gate: run step 7 (n_set < 0: every label). ids: [n]; due: [n], or NULL when
+// the caller wants no flags (the gate still runs).
 inline void track_step(evam_track_state* s, uint32_t thr_key, int max_lost, uint32_t frame, const evam_roi* dets,
                        const int32_t* labels, int n, bool gate, const int32_t* set, int n_set, uint32_t reclassify,
                        uint32_t* ids, uint8_t* due) {
@@ -150,7 +151,9 @@ inline void track_step(evam_track_state* s, uint32_t thr_key, int max_lost, uint
     for (int d = 0; d < n; d++) {
         evam_track_slot* k = d < m && det_slot[d] >= 0 ? &s->slots[det_slot[d]] : nullptr;
         ids[d] = k ? k->id : 0u;
-        if (due) due[d] = gate && track_label_in(labels[d], set, n_set) && track_due(k, frame, reclassify) ? 1 : 0;
+        // the gate runs with or without a due array: classified_at is state, the flag only its report
+        const bool is_due = gate && track_label_in(labels[d], set, n_set) && track_due(k, frame, reclassify);
+        if (due) due[d] = is_due ? 1 : 0;
     }
 }
 

@@ -437,7 +437,8 @@ typedef struct evam_track_item {
 /* One step of the rule on HOST arrays: dets[n_dets] (src_index is ignored) with labels[n_dets] against *state.
  * ids: uint32[n_dets]. due: NULL or uint8[n_dets], 1 for a due detection. The gate runs when classify_labels is given
  * (n_classify_labels >= 0 entries) or when n_classify_labels < 0 with a NULL pointer (every label); a NULL pointer with
- * n_classify_labels == 0 runs no gate (due is all 0). reclassify >= 1. n_dets >= 0 (NULL arrays allowed when 0).
+ * n_classify_labels == 0 runs no gate (due is all 0). The gate runs with or without a due array: classified_at is set
+ * for every due detection either way, as on the device. reclassify >= 1. n_dets >= 0 (NULL arrays allowed when 0).
  * Needs no GPU. Host-only helper. */
 int evam_pp_track_host(evam_track_state* state, const evam_track_cfg* cfg, uint32_t frame, const evam_roi* dets,
                        const int32_t* labels, int n_dets, const int32_t* classify_labels, int n_classify_labels,

@@ -6,78 +6,14 @@ import pytest
 
 import device_rois_cases as C
 import track_ref as R
+from track_cases import SENTINEL, SEQ_SEEDS, Host, check_call, check_states, upload_call
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -3
 
 
 def grid(n, dx=0, step=40, size=30):
     a = np.asarray([((i % 40) * step + dx, (i // 40) * step, size, size) for i in range(n)], np.int32).reshape(-1, 4)
     return a, (np.arange(n, dtype=np.int32) % 3)
-
-
-class Host:
-    """The host twin of a DeviceTracker: one HostTracker per stream slot."""
-
-    def __init__(self, evam, n_slots, cfg):
-        self.evam, self.cfg = evam, cfg
-        self.trk = [evam.native.HostTracker(cfg=cfg) for _ in range(n_slots)]
-
-    def call(self, items, classify, reclassify):
-        """items: [(slot, frame, boxes, labels)] in table order -> (list rows [n, 5], labels, ids, due rows)."""
-        rows, labs, ids, due = [], [], [], []
-        for i, (slot, frame, boxes, labels) in enumerate(items):
-            a, d = self.trk[slot].step(frame, boxes, labels, classify, reclassify)
-            r = np.concatenate([np.full((len(boxes), 1), i, np.int32), np.asarray(boxes, np.int32).reshape(-1, 4)], axis=1)
-            rows.append(r)
-            labs.append(np.asarray(labels, np.int32).reshape(-1))
-            ids.append(a)
-            due.append(r[d])
-        cat = lambda v, shape: np.concatenate(v) if v else np.zeros(shape, np.int32)  # noqa: E731
-        return cat(rows, (0, 5)), cat(labs, (0,)), cat(ids, (0,)).astype(np.uint32), cat(due, (0, 5))
-
-    def state_bytes(self, slot):
-        st = self.trk[slot].state
-        if st.next_id == 0:  # never stepped: the fresh state zeroed memory stands for
-            st = self.evam.native.EvamTrackState()
-            st.next_id = 1
-            for s in st.slots:
-                s.classified_at = self.evam.native.TRACK_NONE
-        return bytes(st)
-
-
-def upload_call(evam, torch, gpu, rows, labs, cap=None, due_cap=None):
-    cap = max(len(rows), 1) if cap is None else cap
-    lst = evam.DeviceRoiList(cap, device=gpu)
-    lst.rois.fill_(SENTINEL)
-    lst.set(rows)
-    labels = torch.full((cap,), SENTINEL, dtype=torch.int32, device=gpu)
-    if len(labs):
-        labels[:len(labs)].copy_(torch.from_numpy(labs))
-    ids = torch.full((cap,), SENTINEL, dtype=torch.int32, device=gpu)
-    due = evam.DeviceRoiList(max(len(rows), 1) if due_cap is None else due_cap, device=gpu)
-    due.rois.fill_(SENTINEL)
-    due.count.fill_(-1)
-    return lst, labels, ids, due
-
-
-def check_call(what, n, want_ids, want_due, ids, due):
-    got = ids.cpu().numpy().view(np.uint32)
-    assert np.array_equal(got[:n], want_ids), f"{what}: ids"
-    assert (got[n:] == 0).all(), f"{what}: ids past the count are 0"
-    count = int(due.count.cpu().numpy().view(np.uint32)[0])
-    assert count == len(want_due), f"{what}: due count {count}, host {len(want_due)}"
-    m = min(count, due.cap)
-    rois = due.rois.cpu().numpy()
-    assert np.array_equal(rois[:m], want_due[:m]), f"{what}: due entries"
-    assert (rois[m:] == SENTINEL).all(), f"{what}: due entries past the count were written"
-    return count
-
-
-def check_states(evam, pp, tracker, host, what):
-    for slot in range(tracker.n_streams):
-        assert bytes(tracker.read_state(pp, slot)) == host.state_bytes(slot), f"{what}: state of slot {slot}"
 
 
 @pytest.mark.parametrize("n_streams,chunks,classify,reclassify,due_cap",
@@ -86,7 +22,8 @@ def check_states(evam, pp, tracker, host, what):
 def test_track_device_equals_host(evam, gpu, n_streams, chunks, classify, reclassify, due_cap):
     import torch
 
-    seqs = R.random_sequences(11 + n_streams, n_streams, sum(chunks))
+    seqs = R.random_sequences(SEQ_SEEDS[n_streams], n_streams, sum(chunks))
+    R.assert_events(R.run_reference(seqs, 8, 0.3)[2], 8)  # on the reference alone: what these sequences reach
     n_slots = n_streams + 2
     slots = [(3 * s + 1) % n_slots for s in range(n_streams)]  # 8 streams: 1 4 7 0 3 6 9 2 — not monotone
     assert len(set(slots)) == n_streams

@@ -5,11 +5,16 @@ slot exhaustion, frames past D detections, long-lived ids, slots reborn) are ass
 Two of the preconditions depend on ``max_lost`` and are asserted only where they can hold: slot exhaustion needs
 ``max_lost`` > 0 (with 0 every unmatched track is freed before the births, so D <= T detections always fit; that sweep
 asserts a slot freed and refilled in one step instead), and an id that survives 10 frames is asserted for ``max_lost``
-8 only: the sweeps with ``max_lost`` 0 and 2 (seeds 2 and 3) do not check longevity."""
+8 only: the sweeps with ``max_lost`` 0 and 2 (seeds 2 and 3) do not check longevity.
+
+Further: the inputs that need as many matching rounds as there are tracks (``track_ref.chain_frames``,
+``disjoint_frames`` at threshold 0.0), sequences of extreme boxes, labels and frame indices at thresholds 0.0, 0.3, 1.0,
+NaN and 2.0 with ``max_lost`` 0, 1 and 8, and the gate with a NULL due array."""
 import numpy as np
 import pytest
 
 import track_ref as R
+from track_cases import host_against_reference as run_host_against_reference
 
 
 def both(evam, max_lost=8, iou=0.3):
@@ -152,15 +157,7 @@ def test_random_sequences(evam, seed, max_lost, classify, reclassify):
     assert len(seqs) == 8 and all(len(fr) == 40 for fr in seqs)
     want, states, ev = R.run_reference(seqs, max_lost, 0.3, classify, reclassify)
     # the preconditions, on the reference alone: a sweep that never reaches them shows nothing
-    assert ev.ties > 0, "no tie between candidates"
-    if max_lost:  # with max_lost 0 every unmatched track is freed before the births: D <= T detections always fit
-        assert ev.exhausted > 0, "the slots never ran out"
-    else:
-        assert ev.refilled_same > 0, "no slot was freed and refilled in one step"
-    assert ev.over_d > 0, "no frame with more than D detections"
-    assert ev.reborn > 0, "no track was dropped and a new id born in its slot"
-    if max_lost == 8:
-        assert ev.longest >= 10, "no id survived 10 frames"
+    R.assert_events(ev, max_lost)
     cfg = evam.native.EvamTrackCfg(max_lost, 0.3)
     for s, frames in enumerate(seqs):
         host = evam.native.HostTracker(cfg=cfg)
@@ -169,3 +166,81 @@ def test_random_sequences(evam, seed, max_lost, classify, reclassify):
             assert ids.tolist() == want[s][f][0], (s, f)
             assert due.tolist() == want[s][f][1], (s, f)
         assert evam.native.track_state_tuple(host.state) == states[s], s
+
+
+def test_null_due_runs_the_gate(evam):
+    """``evam_pp_track_host`` with a classify set and ``due == NULL``: ``classified_at`` is state, so the gate runs as
+    it does with a due array (and as the kernel runs it with no due list)."""
+    N, lib = evam.native, evam.load_library()
+    cfg = N.EvamTrackCfg(8, 0.3)
+    with_due, ref = both(evam)
+    st = N.EvamTrackState()
+    boxes = [(40, 40, 60, 60), (400, 40, 60, 60), (800, 40, 60, 60)]
+    labels = np.asarray([1, 5, 2], np.int32)
+    classify = np.asarray([1, 2], np.int32)
+    for fi in (7, 8, 11, 12, 40):
+        step_both(evam, with_due, ref, fi, boxes, labels, [1, 2], 4)
+        rois = np.zeros((3, 5), np.int32)
+        rois[:, 1:] = boxes
+        ids = np.zeros(3, np.uint32)
+        assert lib.evam_pp_track_host(st, cfg, fi, rois.ctypes.data, labels.ctypes.data, 3, classify.ctypes.data, 2, 4,
+                                      ids.ctypes.data, None) == N.OK
+        assert ids.tolist() == [1, 2, 3]
+        assert N.track_state_tuple(st) == ref.state(), fi
+        assert bytes(st) == bytes(with_due.state), fi
+    assert [s[7] for s in ref.state()[1][:3]] == [40, N.TRACK_NONE, 40]   # due at 7, 11 and 40; label 5 never
+
+
+@pytest.mark.parametrize("n,max_lost", [(128, 8), (127, 1), (128, 0)])
+def test_chain_needs_n_rounds(evam, n, max_lost):
+    frames, ids = R.chain_frames(n, seed=n + max_lost)
+    assert ids != sorted(ids), "the permutation left the chain in slot order"
+    want, ev = run_host_against_reference(evam, [frames], [[3, 4]], max_lost, 0.3, "all", 2)
+    assert ev.rounds >= n, ev.rounds   # one match per round
+    assert want[0][0][0] == list(range(1, n + 1)) and want[0][1][0] == ids
+
+
+def test_two_label_chain(evam):
+    frames, ids = R.two_label_chain_frames(64, seed=5)
+    want, ev = run_host_against_reference(evam, [frames], [[0, 1]], 8, 0.3, [1], 1)
+    assert ev.rounds >= 64, ev.rounds
+    assert want[0][1][0] == ids
+
+
+@pytest.mark.parametrize("max_lost", [0, 1, 8])
+def test_disjoint_grid_at_threshold_zero(evam, max_lost):
+    frames = R.disjoint_frames(128)
+    want, ev = run_host_against_reference(evam, [frames], [[0, 1]], max_lost, 0.0, None, 1)
+    assert ev.rounds >= 128 and ev.ties > 0, (ev.rounds, ev.ties)
+    assert want[0][1][0] == list(range(1, 129))   # every key is 0: lowest slot, then lowest detection
+    # at the default threshold no pair of the same input is a candidate
+    want, ev = run_host_against_reference(evam, [frames], [[0, 1]], 8, 0.3, None, 1)
+    assert ev.rounds == 0 and want[0][1][0] == [0] * 128
+
+
+@pytest.mark.parametrize("max_lost", [0, 1, 8])
+@pytest.mark.parametrize("iou", [0.0, 0.3, 1.0, float("nan"), 2.0])
+def test_extreme_sequences(evam, iou, max_lost):
+    """Boxes and labels at the ends of int32, sides around the 2^20 clamp, frame indices up to 0xFFFFFFFE."""
+    seqs, fi = R.extreme_sequences(21, 2, 30)
+    assert all(f[-1] == R.LAST_FRAME for f in fi)
+    classify, reclassify = ("all", 3) if max_lost != 1 else ([-2**31, 0], 2**31 - 1)
+    _, ev = run_host_against_reference(evam, seqs, fi, max_lost, iou, classify, reclassify)
+    assert ev.ties > 0 and ev.over_d > 0, vars(ev)
+    if max_lost:
+        assert ev.exhausted > 0
+    if iou != iou or iou >= 1.0:
+        assert R.thr_key(iou) == 65536
+
+
+def test_gpu_sequences_reach_the_events():
+    """The sequences of ``test_gpu_track.py::test_track_device_equals_host``, on the reference alone: the events
+    ``test_random_sequences`` asks of its own seeds. Also what makes the chain inputs necessary: no frame of the random
+    sequences, these or the host sweep's, needs more than two matching rounds."""
+    from track_cases import SEQ_SEEDS
+
+    for n_streams, seed in SEQ_SEEDS.items():
+        ev = R.run_reference(R.random_sequences(seed, n_streams, 16), 8, 0.3)[2]
+        R.assert_events(ev, 8)
+        assert 1 <= ev.rounds <= 2, (seed, ev.rounds)
+    assert R.run_reference(R.random_sequences(1), 8, 0.3)[2].rounds == 2
