@@ -15,7 +15,8 @@ hand-written HIP kernels for gfx950 behind the C ABI in ``include/evam_pp.h``.
 """
 import sys as _sys
 
-from ._native import HostTracker, PreProcError, jpeg_bound, jpeg_header, jpeg_planes_ok, load_library  # noqa: F401
+from ._native import (DetectionOutputConfig, HostTracker, PreProcError, detection_output_host, jpeg_bound,  # noqa: F401
+                      jpeg_header, jpeg_planes_ok, load_library)
 from .preproc import (DeviceRoiList, DeviceTracker, HipPreProcessor, Image, ImageBatch, JpegInfo, PreProcInfo, Roi,  # noqa: F401
                       RoiBatch, Transform, create_preprocessor, jpeg_info, output_dtype, plane_layout, tensor_layout)
 from . import _native as native  # noqa: F401

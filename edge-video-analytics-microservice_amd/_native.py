@@ -11,6 +11,7 @@ pointers and streams created by torch are then valid here.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
 import sys
 
@@ -61,9 +62,11 @@ EXPORTED_SYMBOLS = (
     "evam_pp_decode_jpeg_planes", "evam_pp_decode_jpeg_planes_host",
     "evam_pp_track_host", "evam_pp_tracker_create", "evam_pp_tracker_destroy", "evam_pp_tracker_reset",
     "evam_pp_tracker_read", "evam_pp_track_device_rois", "evam_pp_ssd_rois_ex",
+    "evam_pp_detection_output", "evam_pp_detection_output_host",
 )
 # ... and the one that returns size_t (tests/test_abi.py reads the header's int / void / const char* declarations)
 EXPORTED_SYMBOLS_SIZE_T = ("evam_pp_jpeg_bound",)
+EXPORTED_SYMBOLS_FLOAT = ("evam_pp_expf",)  # ... and the one that returns float
 
 c_i32 = ctypes.c_int32
 
@@ -134,18 +137,29 @@ class EvamTrackItem(ctypes.Structure):
     _fields_ = [("stream", c_i32), ("frame", ctypes.c_uint32)]
 
 
+DETOUT_MAX_TOP_K, DETOUT_MAX_CLASSES = 1024, 256  # EVAM_DETOUT_*
+
+
+class EvamDetoutCfg(ctypes.Structure):
+    """``evam_detout_cfg``: what ``evam_pp_detection_output`` reads of an SSD DetectionOutput layer's attributes."""
+
+    _fields_ = [("num_classes", c_i32), ("background_label", c_i32), ("top_k", c_i32), ("keep_top_k", c_i32),
+                ("confidence_threshold", ctypes.c_float), ("nms_threshold", ctypes.c_float)]
+
+
 # evam_pp_stats.kernels bits (include/evam_pp.h evam_kernel_family)
 KERNEL_GENERIC, KERNEL_ROWS, KERNEL_STAGED, KERNEL_WAVE = 1, 2, 4, 8
 KERNEL_STRIP, KERNEL_BAND, KERNEL_ROI = 16, 32, 64
 KERNEL_JPEG = 128
 KERNEL_JPEG_DEC = 256
+KERNEL_DETOUT = 512
 
 JPEG_HEADER_LEN = 623  # SOI .. SOS of every file evam_pp_encode_jpeg writes
 
 
 STRUCT_SIZES = {EvamImage: 48, EvamRoi: 20, EvamPreproc: 56, EvamTensor: 40, EvamTransform: 40, EvamStats: 32,
                 EvamRoiList: 24, EvamJpegInfo: 28, EvamTrackSlot: 32, EvamTrackState: 4128, EvamTrackCfg: 8,
-                EvamTrackItem: 8}
+                EvamTrackItem: 8, EvamDetoutCfg: 24}
 
 _LIB = None
 
@@ -227,6 +241,15 @@ def _declare(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.evam_pp_track_device_rois.restype = ctypes.c_int
     lib.evam_pp_ssd_rois_ex.argtypes = [vp] + ssd + [vp]
     lib.evam_pp_ssd_rois_ex.restype = ctypes.c_int
+    if not hasattr(lib, "evam_pp_detection_output"):  # an A/B variant built before DetectionOutput
+        return lib
+    det = [vp, vp, vp, ctypes.c_int, ctypes.c_int, P(EvamDetoutCfg), vp, vp]
+    lib.evam_pp_detection_output.argtypes = [vp] + det
+    lib.evam_pp_detection_output.restype = ctypes.c_int
+    lib.evam_pp_detection_output_host.argtypes = det
+    lib.evam_pp_detection_output_host.restype = ctypes.c_int
+    lib.evam_pp_expf.argtypes = [ctypes.c_float]
+    lib.evam_pp_expf.restype = ctypes.c_float
     return lib
 
 
@@ -494,6 +517,175 @@ def track_state_tuple(state: EvamTrackState):
         return 1, [(0, 0, 0, 0, 0, 0, 0, TRACK_NONE)] * TRACK_SLOTS
     return int(state.next_id), [(int(s.id), int(s.label), int(s.x), int(s.y), int(s.w), int(s.h), int(s.lost),
                                  int(s.classified_at)) for s in state.slots]
+
+
+# OpenVINO DetectionOutput-1 attributes the rule has one served value for (include/evam_pp.h): name -> that value
+_DETOUT_FIXED = {"code_type": "caffe.PriorBoxParameter.CENTER_SIZE", "share_location": True, "normalized": True,
+                 "variance_encoded_in_target": False, "clip_before_nms": False, "clip_after_nms": False,
+                 "decrease_label_id": False}
+# ... and those that do not change the result for that set (read and ignored)
+_DETOUT_IGNORED = ("input_height", "input_width", "objectness_score")
+
+
+def _detout_bool(name: str, v) -> bool:
+    if isinstance(v, str):
+        t = v.strip().lower()
+        if t in ("true", "1"):
+            return True
+        if t in ("false", "0"):
+            return False
+        raise PreProcError(ERR_INVALID_ARG, f"detection_output: {name} {v!r} is no boolean")
+    return bool(v)
+
+
+@dataclasses.dataclass(frozen=True)
+class DetectionOutputConfig:
+    """The attributes of an SSD ``DetectionOutput`` layer that ``evam_pp_detection_output`` serves (``evam_detout_cfg``).
+    Build it with :meth:`from_attributes` from the OpenVINO attribute names."""
+
+    num_classes: int
+    keep_top_k: int
+    background_label: int = 0
+    top_k: int = 400
+    confidence_threshold: float = 0.01
+    nms_threshold: float = 0.45
+
+    @classmethod
+    def from_attributes(cls, attrs: dict) -> "DetectionOutputConfig":
+        """From a dict of OpenVINO ``DetectionOutput-1`` attributes: ``num_classes`` and ``keep_top_k`` (an int or a
+        one-element list) are required; ``background_label_id`` (0), ``top_k`` (400), ``confidence_threshold`` (0.01)
+        and ``nms_threshold`` (0.45) have the defaults of the reference's detectors. Every attribute set the rule does
+        not serve is refused with ``ERR_UNSUPPORTED`` and the reason; an unknown attribute or a value outside the
+        limits with ``ERR_INVALID_ARG``."""
+        if not isinstance(attrs, dict):
+            raise PreProcError(ERR_INVALID_ARG, f"detection_output: the attributes are a dict, not {type(attrs).__name__}")
+        a = dict(attrs)
+        for name in _DETOUT_IGNORED:
+            a.pop(name, None)
+        for name, served in _DETOUT_FIXED.items():
+            if name not in a:
+                continue
+            v = a.pop(name)
+            if name == "code_type":
+                if str(v).rsplit(".", 1)[-1].upper() != "CENTER_SIZE":
+                    raise PreProcError(ERR_UNSUPPORTED, f"detection_output: code_type {v!r} is not served; only "
+                                                        f"CENTER_SIZE box deltas are decoded")
+            elif _detout_bool(name, v) != served:
+                raise PreProcError(ERR_UNSUPPORTED, f"detection_output: {name} = {v!r} is not served; the rule is "
+                                                    f"defined for {name} = {str(served).lower()} only")
+        for name in ("num_classes", "keep_top_k"):
+            if name not in a:
+                raise PreProcError(ERR_INVALID_ARG, f"detection_output: the attribute {name} is required")
+        keep = a.pop("keep_top_k")
+        if isinstance(keep, (list, tuple)):
+            if len(keep) != 1:
+                raise PreProcError(ERR_UNSUPPORTED, f"detection_output: keep_top_k {keep!r}: one value is served")
+            keep = keep[0]
+        try:
+            cfg = cls(num_classes=int(a.pop("num_classes")), keep_top_k=int(keep),
+                      background_label=int(a.pop("background_label_id", 0)), top_k=int(a.pop("top_k", 400)),
+                      confidence_threshold=float(a.pop("confidence_threshold", 0.01)),
+                      nms_threshold=float(a.pop("nms_threshold", 0.45)))
+        except (TypeError, ValueError) as e:
+            raise PreProcError(ERR_INVALID_ARG, f"detection_output: {e}") from None
+        if a:
+            raise PreProcError(ERR_INVALID_ARG, f"detection_output: unknown attribute(s) {', '.join(sorted(a))}")
+        for name in ("top_k", "keep_top_k"):
+            if getattr(cfg, name) == -1:
+                raise PreProcError(ERR_UNSUPPORTED, f"detection_output: {name} = -1 (\"all\") is not served; give a "
+                                                    f"value in 1..{DETOUT_MAX_TOP_K}")
+        cfg.check()
+        return cfg
+
+    def check(self) -> None:
+        """The limits of ``include/evam_pp.h`` that do not depend on a call's shapes."""
+        import math
+
+        def bad(msg):
+            raise PreProcError(ERR_INVALID_ARG, "detection_output: " + msg)
+
+        if not 2 <= self.num_classes <= DETOUT_MAX_CLASSES:
+            bad(f"num_classes {self.num_classes} outside 2..{DETOUT_MAX_CLASSES}")
+        if not -1 <= self.background_label < self.num_classes:
+            bad(f"background_label_id {self.background_label} outside -1..{self.num_classes - 1}")
+        for name in ("top_k", "keep_top_k"):
+            if not 1 <= getattr(self, name) <= DETOUT_MAX_TOP_K:
+                bad(f"{name} {getattr(self, name)} outside 1..{DETOUT_MAX_TOP_K}")
+        if not (math.isfinite(self.confidence_threshold) and self.confidence_threshold >= 0):
+            bad(f"confidence_threshold {self.confidence_threshold} must be finite and >= 0")
+        if not math.isfinite(self.nms_threshold):
+            bad(f"nms_threshold {self.nms_threshold} must be finite")
+
+    def to_c(self) -> EvamDetoutCfg:
+        return EvamDetoutCfg(int(self.num_classes), int(self.background_label), int(self.top_k), int(self.keep_top_k),
+                             float(self.confidence_threshold), float(self.nms_threshold))
+
+
+def _detout_cfg(cfg) -> EvamDetoutCfg:
+    if isinstance(cfg, EvamDetoutCfg):
+        return cfg
+    if isinstance(cfg, dict):
+        cfg = DetectionOutputConfig.from_attributes(cfg)
+    if not isinstance(cfg, DetectionOutputConfig):
+        raise PreProcError(ERR_INVALID_ARG, f"detection_output: cfg is a DetectionOutputConfig or a dict of attributes, "
+                                            f"not {type(cfg).__name__}")
+    return cfg.to_c()
+
+
+def detout_shapes(loc_shape, conf_shape, priors_shape, num_classes: int):
+    """``(n, p)`` of raw SSD heads: ``loc`` ``[N, P*4]`` or ``[N, P, 4]``, ``conf`` ``[N, P*C]`` or ``[N, P, C]``,
+    ``priors`` ``[2, P*4]``, ``[1, 2, P*4]`` or ``[2, P, 4]``. ``ERR_INVALID_ARG`` when they do not agree."""
+    def numel(shape):
+        k = 1
+        for d in shape:
+            k *= int(d)
+        return k
+
+    def bad(msg):
+        raise PreProcError(ERR_INVALID_ARG, "detection_output: " + msg)
+
+    if len(loc_shape) not in (2, 3) or len(conf_shape) not in (2, 3):
+        bad(f"loc {tuple(loc_shape)} / conf {tuple(conf_shape)}: [N, P*4] / [N, P*C] (or [N, P, 4] / [N, P, C]) expected")
+    n = int(loc_shape[0])
+    if n < 1 or int(conf_shape[0]) != n:
+        bad(f"loc {tuple(loc_shape)} and conf {tuple(conf_shape)} differ in their batch size")
+    per = numel(loc_shape[1:])
+    if per % 4 or per == 0 or (len(loc_shape) == 3 and int(loc_shape[2]) != 4):
+        bad(f"loc {tuple(loc_shape)}: four deltas per prior expected")
+    p = per // 4
+    if numel(conf_shape[1:]) != p * num_classes or (len(conf_shape) == 3 and int(conf_shape[2]) != num_classes):
+        bad(f"conf {tuple(conf_shape)}: {p} priors x {num_classes} classes expected")
+    ps = tuple(int(d) for d in priors_shape)
+    if ps[:1] == (1,) and len(ps) > 2:
+        ps = ps[1:]
+    if numel(ps) != 2 * p * 4 or ps[0] != 2 or (len(ps) == 3 and ps[2] != 4) or len(ps) not in (2, 3):
+        bad(f"priors {tuple(priors_shape)}: [2, {p * 4}] (boxes, then variances) expected")
+    return n, p
+
+
+def detection_output_host(loc, conf, priors, cfg):
+    """``evam_pp_detection_output_host``: SSD DetectionOutput of raw heads on numpy arrays (shapes as for
+    :func:`detout_shapes`; float32, other float types are converted). ``cfg``: a :class:`DetectionOutputConfig` or a
+    dict of attributes. Returns ``(float32 [N, keep_top_k, 7] blob, uint32 [N] survivor counts)``. Needs no GPU."""
+    import numpy as np
+
+    lib = load_library()
+    c = _detout_cfg(cfg)
+    a = np.ascontiguousarray(loc, dtype=np.float32)
+    b = np.ascontiguousarray(conf, dtype=np.float32)
+    pr = np.ascontiguousarray(priors, dtype=np.float32)
+    n, p = detout_shapes(a.shape, b.shape, pr.shape, c.num_classes)
+    k = max(int(c.keep_top_k), 1)
+    out = np.full((n, k, 7), np.nan, np.float32)
+    counts = np.full(n, 0xFFFFFFFF, np.uint32)
+    check(lib, lib.evam_pp_detection_output_host(a.ctypes.data, b.ctypes.data, pr.ctypes.data, n, p, ctypes.byref(c),
+                                                 out.ctypes.data, counts.ctypes.data))
+    return out, counts
+
+
+def expf(x: float) -> float:
+    """``evam_pp_expf``: the exp the DetectionOutput decode uses (the same bits on the host and the device)."""
+    return float(load_library().evam_pp_expf(float(x)))
 
 
 class PreProcError(RuntimeError):

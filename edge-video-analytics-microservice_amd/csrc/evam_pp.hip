@@ -27,8 +27,8 @@
 //
 // One translation unit. This file: the seven kernel families, the kernel tables, launch_kernel and resident_per_cu
 // (HipKernels, the planner's HIP backend), HipRings, struct evam_pp, run_impl and the entry points. Included:
-// evam_params.h (kernel-argument structs) and evam_plan.h (the host planner), both HIP-free; the JPEG, JPEG-decode and
-// tracker kernels and entry points (evam_*_kernels.h, evam_*_api.h).
+// evam_params.h (kernel-argument structs) and evam_plan.h (the host planner), both HIP-free; the JPEG, JPEG-decode,
+// tracker and DetectionOutput kernels and entry points (evam_*_kernels.h, evam_*_api.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -56,6 +56,7 @@
 #include "evam_clip_simd.h"
 #include "evam_jpeg_dec.h"
 #include "evam_track.h"
+#include "evam_detout.h"
 
 namespace {
 
@@ -3388,6 +3389,7 @@ using PinRing = PinRingT<HipRings>;
 #include "evam_jpeg_kernels.h"
 #include "evam_jpeg_dec_kernels.h"
 #include "evam_track_kernels.h"
+#include "evam_detout_kernels.h"
 
 // evam_pp_decode_jpeg: device scratch (grown on demand, reused) and the pinned staging of the file bytes.
 enum { kJdUp = 0, kJdStream, kJdFirst, kJdSlots, kJdCoef, kJdPlanes, kJdCount };
@@ -3464,6 +3466,8 @@ struct evam_pp {
     DescRing ring_ssd;             // evam_pp_ssd_rois' block: a ring of its own, so that a detect -> classify chain that
                                    // alternates it with evam_pp_run_device_rois' block re-uploads neither when unchanged
     DescRing ring_trk;             // evam_pp_track_device_rois' block (stream runs, item table, classify label set)
+    void* dev_detout = nullptr;    // evam_pp_detection_output: per-class kept counts and keys (kernels only, as above)
+    size_t dev_detout_cap = 0;
 };
 
 namespace {
@@ -3570,6 +3574,7 @@ void evam_pp_destroy(evam_pp* h) {
     if (h->jdec.pin_ev) (void)hipEventDestroy(h->jdec.pin_ev);
     if (h->dev_recs) (void)hipFree(h->dev_recs);
     if (h->dev_cnt) (void)hipFree(h->dev_cnt);
+    if (h->dev_detout) (void)hipFree(h->dev_detout);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -4576,3 +4581,4 @@ int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, cons
 #include "evam_jpeg_api.h"
 #include "evam_jpeg_dec_api.h"
 #include "evam_track_api.h"
+#include "evam_detout_api.h"

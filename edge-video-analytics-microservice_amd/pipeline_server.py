@@ -224,6 +224,14 @@ class InferenceModel:
     ``[N, C]`` tensor. ``input_size`` is ``(W, H)``. Labels and pre-processing come from the
     model-proc (``models_list/*.json``). ``out_dtype``: ``"f32"`` (default), ``"u8"``, or, for a model bound from
     an ``FP16`` IR, ``"f16"`` / ``"bf16"``: the blob is then written in that type by the kernels (no cast pass).
+
+    ``detection_output`` (detectors only; default off): the attributes of the SSD ``DetectionOutput`` layer the model
+    was ported without (OpenVINO names: ``num_classes``, ``keep_top_k``, ``top_k``, ``background_label_id``,
+    ``confidence_threshold``, ``nms_threshold``, ...) plus ``"priors"``, the constant ``[2, P*4]`` prior tensor (boxes,
+    then variances; array or tensor). ``fn`` then returns the raw heads, ``(loc [N, P*4], conf [N, P*C])`` or
+    ``{"loc": ..., "conf": ...}`` (probabilities: softmax applied), and the detect stage turns them into the blob on
+    the device (``HipPreProcessor.detection_output``) behind the model call. An attribute set the layer's rule
+    (``include/evam_pp.h``) does not serve is refused when the pipeline starts.
     """
 
     fn: object
@@ -232,6 +240,7 @@ class InferenceModel:
     out_dtype: str = "f32"
     name: str | None = None
     layout: str = "nchw"  # "nhwc": the stage packs into a torch.channels_last blob, handed to ``fn`` unchanged
+    detection_output: dict | None = None  # SSD DetectionOutput attributes + "priors": ``fn`` returns raw heads
 
     def preproc_info(self, overrides: dict | None = None):
         from .preproc import PreProcInfo
@@ -251,6 +260,59 @@ class InferenceModel:
 
     def postprocs(self):
         return list((self.model_proc or {}).get("output_postproc", []))
+
+
+def detection_output_spec(model):
+    """``(DetectionOutputConfig, float32 priors [2, P*4])`` of a model's ``detection_output``, or None when it is
+    unset. Refuses a bad attribute set or prior tensor (``PreProcError``); parsed once per model."""
+    import numpy as np
+
+    spec = model.detection_output
+    if spec is None:
+        return None
+    cached = model.__dict__.get("_detout_spec")
+    if cached is not None and cached[0] is spec:
+        return cached[1], cached[2]
+    if not isinstance(spec, dict):
+        raise PreProcError(N.ERR_INVALID_ARG, f"detection_output must be a dict of attributes, got {type(spec).__name__}")
+    attrs = dict(spec)
+    priors = attrs.pop("priors", None)
+    if priors is None:
+        raise PreProcError(N.ERR_INVALID_ARG, "detection_output needs \"priors\": the [2, P*4] prior tensor")
+    cfg = N.DetectionOutputConfig.from_attributes(attrs)
+    if hasattr(priors, "detach"):
+        priors = priors.detach().float().cpu().numpy()
+    pr = np.ascontiguousarray(priors, dtype=np.float32)
+    if pr.ndim > 2 and pr.shape[0] == 1:
+        pr = pr[0]
+    if pr.ndim not in (2, 3) or pr.shape[0] != 2 or pr.size == 0 or pr.size % 8 or (pr.ndim == 3 and pr.shape[2] != 4):
+        raise PreProcError(N.ERR_INVALID_ARG, f"detection_output: priors {tuple(np.shape(priors))}: [2, P*4] (boxes, "
+                                              f"then variances) expected")
+    pr = pr.reshape(2, -1)
+    model.__dict__["_detout_spec"] = (spec, cfg, pr)
+    return cfg, pr
+
+
+def model_detection_output(model, spec, raw, pp, device: int):
+    """The ``[N, K, 7]`` blob of the raw heads ``raw`` a model with ``detection_output`` returned: enqueued on the
+    device behind the model call (same stream), priors uploaded once per (model, device)."""
+    import torch
+
+    cfg, pr = spec
+    if isinstance(raw, dict):
+        loc, conf = raw.get("loc"), raw.get("conf")
+    elif isinstance(raw, (tuple, list)) and len(raw) == 2:
+        loc, conf = raw
+    else:
+        loc = conf = None
+    if not (isinstance(loc, torch.Tensor) and isinstance(conf, torch.Tensor)):
+        raise PreProcError(N.ERR_INVALID_ARG, f"{model.name or 'model'}: with detection_output set, fn returns (loc, conf) "
+                                              f"or {{\"loc\", \"conf\"}} device tensors, got {type(raw).__name__}")
+    cache = model.__dict__.setdefault("_detout_priors", {})
+    ent = cache.get(device)
+    if ent is None or ent[0] is not pr:
+        ent = cache[device] = (pr, torch.from_numpy(pr).to(f"cuda:{device}"))
+    return pp.detection_output(loc.detach(), conf.detach(), ent[1], cfg)
 
 
 def ir_input_size(xml_path: str):
@@ -984,6 +1046,18 @@ class _InferenceStage:
 
 
 class DetectStage(_InferenceStage):
+    def __init__(self, el: Element, server, device: int, slot: int = 0):
+        super().__init__(el, server, device, slot)
+        self._detout = detection_output_spec(self.model)  # refused here: before anything runs
+
+    def infer(self, out, pp):
+        """The model call on the input tensor ``out``: its ``[N, K, 7]`` blob, computed on the device from the raw
+        heads when the model has ``detection_output`` set."""
+        raw = self.model.fn(out)
+        if self._detout is None:
+            return raw
+        return model_detection_output(self.model, self._detout, raw, pp, self.device)
+
     def prepare(self, items):
         """items: list of (frame_index, Image, FrameResult) -> (the frames to infer, units)."""
         run = [it for it in items if it[0] % self.interval == 0] if self.interval > 1 else items
@@ -1006,7 +1080,7 @@ class DetectStage(_InferenceStage):
         the model's output)."""
         out = self._tensor(len(run))
         xfs = pp.convert([img for _, img, _ in run], out, self.info, want_transform="lazy")
-        return out, xfs, self.model.fn(out)
+        return out, xfs, self.infer(out, pp)
 
     def labels(self):
         labels = None

@@ -651,6 +651,57 @@ class HipPreProcessor:
             N.check(self._lib, rc)
         return out_list
 
+    def detection_output(self, loc, conf, priors, cfg, out=None, counts=None):
+        """SSD DetectionOutput of a detector's raw heads, on the device (``evam_pp_detection_output``: the rule of
+        ``include/evam_pp.h``): the ``[N, keep_top_k, 7]`` blob :meth:`detections_to_rois` and
+        ``postproc.parse_ssd_batch`` read.
+
+        ``loc``: box deltas ``[N, P*4]`` (or ``[N, P, 4]``); ``conf``: class probabilities ``[N, P*C]`` (or
+        ``[N, P, C]``), softmax applied; ``priors``: ``[2, P*4]`` (``[1, 2, P*4]``, ``[2, P, 4]``), boxes then variances.
+        All are CUDA tensors on the handle's device; fp16 / bf16 heads are cast with ``.float()`` here, any other dtype
+        and a non-contiguous tensor are ``ERR_INVALID_ARG`` (no silent copy). ``cfg``: a
+        :class:`DetectionOutputConfig` or a dict of the layer's attributes. ``out``: a contiguous float32
+        ``[N, keep_top_k, 7]`` tensor to fill (default: a new one); ``counts``: None, or a contiguous int32 tensor of
+        ``>= N`` elements that receives each image's survivor count. Returns ``out``. Asynchronous, as
+        :meth:`convert`."""
+        torch = self._torch
+        c = N._detout_cfg(cfg)
+
+        def head(t, what):
+            if not isinstance(t, torch.Tensor):
+                raise PreProcError(N.ERR_INVALID_ARG, f"detection_output: {what} must be a tensor, got {type(t).__name__}")
+            self._check_device(t)
+            if not t.is_contiguous():
+                raise PreProcError(N.ERR_INVALID_ARG, f"detection_output: {what} {tuple(t.shape)} is not contiguous")
+            if t.dtype in (torch.float16, torch.bfloat16):
+                return t.float()
+            if t.dtype != torch.float32:
+                raise PreProcError(N.ERR_INVALID_ARG, f"detection_output: {what} must be float32 (or fp16 / bf16), got {t.dtype}")
+            return t
+
+        loc, conf, priors = head(loc, "loc"), head(conf, "conf"), head(priors, "priors")
+        n, p = N.detout_shapes(loc.shape, conf.shape, priors.shape, c.num_classes)
+        k = int(c.keep_top_k)
+        if out is None:
+            if not 1 <= k <= N.DETOUT_MAX_TOP_K:
+                raise PreProcError(N.ERR_INVALID_ARG, f"detection_output: keep_top_k {k} outside 1..{N.DETOUT_MAX_TOP_K}")
+            out = torch.empty((n, k, 7), dtype=torch.float32, device=loc.device)
+        else:
+            self._check_device(out)
+            if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, k, 7):
+                raise PreProcError(N.ERR_INVALID_ARG, f"detection_output: out must be a contiguous float32 [{n}, {k}, 7] "
+                                                      f"tensor, got {out.dtype} {tuple(out.shape)}")
+        if counts is not None:
+            self._check_i32(counts, n, "detection_output: counts")
+        self._bind_stream()
+        rc = self._lib.evam_pp_detection_output(
+            self._h, ctypes.c_void_p(loc.data_ptr()), ctypes.c_void_p(conf.data_ptr()), ctypes.c_void_p(priors.data_ptr()),
+            n, p, ctypes.byref(c), ctypes.c_void_p(out.data_ptr()),
+            None if counts is None else ctypes.c_void_p(counts.data_ptr()))
+        if rc:
+            N.check(self._lib, rc)
+        return out
+
     def _check_i32(self, t, n: int, what: str):
         torch = self._torch
         if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:

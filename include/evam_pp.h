@@ -170,7 +170,8 @@ enum evam_kernel_family {
     EVAM_KERNEL_GENERIC = 1, EVAM_KERNEL_ROWS = 2, EVAM_KERNEL_STAGED = 4, EVAM_KERNEL_WAVE = 8,
     EVAM_KERNEL_STRIP = 16, EVAM_KERNEL_BAND = 32, EVAM_KERNEL_ROI = 64,
     EVAM_KERNEL_JPEG = 128, /* evam_pp_encode_jpeg: set beside the bits of the export that staged the BGR frame */
-    EVAM_KERNEL_JPEG_DEC = 256 /* evam_pp_decode_jpeg: the only bit after a decode call */
+    EVAM_KERNEL_JPEG_DEC = 256, /* evam_pp_decode_jpeg: the only bit after a decode call */
+    EVAM_KERNEL_DETOUT = 512 /* evam_pp_detection_output: the only bit after such a call */
 };
 
 enum evam_pp_option {
@@ -485,6 +486,70 @@ int evam_pp_track_device_rois(evam_pp* h, evam_pp_tracker* t, const evam_roi_lis
 int evam_pp_ssd_rois_ex(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs,
                         const evam_transform* xf, int tensor_w, int tensor_h, float threshold,
                         const int32_t* labels, int n_labels, const evam_roi_list* list, int32_t* out_labels);
+
+/* ---- SSD DetectionOutput: raw detector heads -> the [N, K, 7] rows evam_pp_ssd_rois and the host parser read (the
+ * last layer of the OpenVINO IR of every detector the reference lists, models_list/models.list.yml; a PyTorch port of
+ * such a model ends at its box deltas and class probabilities). Symbols and one new struct added, no existing struct
+ * changed: the ABI version stays 3.
+ *
+ * OpenVINO's layer is third party and not vendored; the rule below is this project's own and follows
+ * the published DetectionOutput-1 semantics for code_type = CENTER_SIZE, share_location = true, normalized = true,
+ * variance_encoded_in_target = false, no clipping, decrease_label_id = false. No byte parity with OpenVINO is claimed.
+ *
+ * Inputs, all float32: loc[N][P][4] box deltas; conf[N][P][C] probabilities, prior-major and class-minor, softmax
+ * already applied; priors[2][P][4] shared by the batch, row 0 the prior boxes (xmin, ymin, xmax, ymax), row 1 the four
+ * variances of each prior. Per image n, in float32 with no contraction:
+ *   1. class c != background_label, prior p: s = conf[n][p][c] is a candidate when s is finite and
+ *      s > confidence_threshold;
+ *   2. within a class: score descending, ties to the lower p; only the first top_k take part;
+ *   3. a participating candidate is decoded: pw = pxmax - pxmin, ph = pymax - pymin, pcx = (pxmin + pxmax) * 0.5f,
+ *      pcy alike, cx = ((v0 * l0) * pw) + pcx, cy = ((v1 * l1) * ph) + pcy, w = evam_expf(v2 * l2) * pw,
+ *      h = evam_expf(v3 * l3) * ph, box = (cx - w * 0.5f, cy - h * 0.5f, cx + w * 0.5f, cy + h * 0.5f). evam_expf is
+ *      the library's own exp (evam_pp_expf): +, *, one round-to-nearest and an exponent insert, the same bits on the
+ *      host and the device, at most 2 ulp from the correctly rounded value on [-20, 20]. A candidate whose box has a
+ *      non-finite value is dropped: it does not take part and does not suppress;
+ *   4. greedy NMS within the class, in the order of 2: a candidate is kept when jaccard(it, k) <= nms_threshold for
+ *      every kept k before it. jaccard is 0 when the boxes are disjoint (b.xmin > a.xmax || b.xmax < a.xmin, likewise
+ *      in y) or when iw <= 0 || ih <= 0; otherwise inter / ((area_a + area_b) - inter), one IEEE float division;
+ *      area = 0 for xmax < xmin || ymax < ymin, otherwise (xmax - xmin) * (ymax - ymin);
+ *   5. of all kept candidates of the image the keep_top_k with the highest score survive; ties go to the lower class,
+ *      then the lower p;
+ *   6. out[n][K][7], K = keep_top_k: the survivors ordered by class ascending, then score descending, then p
+ *      ascending, one row (float(n), float(c), s, xmin, ymin, xmax, ymax) each; EVERY row from the survivor count on
+ *      is (-1, 0, 0, 0, 0, 0, 0), so the whole block is defined. counts[n] is the survivor count.
+ * Limits (EVAM_PP_ERR_INVALID_ARG outside them, the message names the argument): n 1..65535; p >= 1 and
+ * p * num_classes < 2^31; num_classes 2..EVAM_DETOUT_MAX_CLASSES; background_label -1 (none) .. num_classes - 1;
+ * top_k and keep_top_k 1..EVAM_DETOUT_MAX_TOP_K (OpenVINO's -1, "all", is refused); confidence_threshold finite and
+ * >= 0; nms_threshold finite. Any other attribute set of the layer (CORNER code types, per-class locations, clipping,
+ * ...) cannot be expressed in evam_detout_cfg; the Python binding refuses it with EVAM_PP_ERR_UNSUPPORTED. */
+#define EVAM_DETOUT_MAX_TOP_K 1024
+#define EVAM_DETOUT_MAX_CLASSES 256
+
+typedef struct evam_detout_cfg { /* 24 B */
+    int32_t num_classes;        /* C */
+    int32_t background_label;   /* -1: none */
+    int32_t top_k;
+    int32_t keep_top_k;         /* K */
+    float confidence_threshold;
+    float nms_threshold;
+} evam_detout_cfg;
+
+/* loc, conf, priors, out (float[n][keep_top_k][7]) and counts (uint32[n], or NULL) are DEVICE pointers. Two launches:
+ * one 256-thread workgroup per (image, class) selects, orders, decodes and suppresses; one per image merges and
+ * writes. The result does not depend on scheduling (no float atomics, no order taken from an atomic counter).
+ * Scratch (n * num_classes * top_k keys of 8 bytes) belongs to the handle, grows on demand and is reused
+ * (EVAM_PP_ERR_OOM when it cannot; growing waits for the work that uses the old buffer). Asynchronous on the handle's
+ * stream; the host reads no device memory. evam_pp_stats.kernels reports EVAM_KERNEL_DETOUT, n_launches 2. */
+int evam_pp_detection_output(evam_pp* h, const float* loc, const float* conf, const float* priors, int n, int p,
+                             const evam_detout_cfg* cfg, float* out, uint32_t* counts);
+
+/* evam_pp_detection_output on HOST arrays: the same shared arithmetic, driven sequentially. Needs no GPU.
+ * Host-only helper. */
+int evam_pp_detection_output_host(const float* loc, const float* conf, const float* priors, int n, int p,
+                                  const evam_detout_cfg* cfg, float* out, uint32_t* counts);
+
+/* The exp of step 3, so that tests and callers can reach it. Host-only helper. */
+float evam_pp_expf(float x);
 
 #ifdef __cplusplus
 }
