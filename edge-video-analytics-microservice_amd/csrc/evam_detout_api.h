@@ -1,5 +1,5 @@
 // evam_pp_detection_output / evam_pp_detection_output_host / evam_pp_expf: the host side of SSD DetectionOutput.
-// Included at the end of evam_pp.hip (needs struct evam_pp, fail, grow_device); kernels in evam_detout_kernels.h.
+// Included at the end of evam_pp.hip (needs struct evam_pp, fail, and grow_device of evam_rois_api.h); kernels in evam_detout_kernels.h.
 #pragma once
 
 namespace {

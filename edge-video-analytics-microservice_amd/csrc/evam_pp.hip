@@ -8,27 +8,31 @@
 // The C ABI is declared in include/evam_pp.h; SURVEY.md §8 is the scope table.
 //
 // Design (DESIGN.md has the full write-up):
-//  * One launch per (source format, call). One 256-thread workgroup per (item, output tile of TW x TH
-//    pixels). The workgroup
-//      1. computes the OpenCV coefficient tables for its tile columns/rows on the device, in the exact
-//         double/float operation sequence of hal::resize (no FMA contraction: built -ffp-contract=off);
-//      2. stages the source footprint of the tile — two luma rows and two chroma rows per output row,
-//         duplicated rows skipped, columns [first tap, last tap] aligned out to 16 B — from HBM into LDS
-//         with 128-bit coalesced loads;
-//      3. for every output pixel converts its four taps to BGR (BT.601 20-bit fixed point), runs the
-//         11-bit horizontal pass and the VResizeLinear 32s->8u vertical pass, maps the u8 result
-//         through the per-channel normalisation LUT (fp32 out) and stores planar NCHW, or, for a tensor with
-//         layout = EVAM_LAYOUT_NHWC, the slot's interleaved H x W x 3 image (a NHWC template parameter on the
-//         strip, band, wave and generic kernels: only the store epilogue differs). fp16 / bf16 output
-//         (EVAM_DTYPE_F16 / _BF16) is the same path with a table of 16-bit patterns and 2-byte stores (OUT = 2 on
-//         the generic, strip, ROI and wave kernels; interleaved 16-bit output: the generic kernel only).
-//  * Letterbox padding tiles never touch the source. Nothing is MFMA-shaped: the path is HBM-bound
-//    integer gather work (roofline: HBM, 8 TB/s).
+//  * One launch per (source format, call) and group of items; the host planner (evam_plan.h) picks the kernel family
+//    per group (DESIGN.md §4 has the table): strip, band, wave, staged or rows for items of one geometry, roi for
+//    per-item geometry, and the generic kernel for whatever those do not plan.
+//  * Every family computes the same integers: the OpenCV coefficient tables in the exact double/float operation
+//    sequence of hal::resize (no FMA contraction: built -ffp-contract=off), the four taps of an output pixel converted
+//    to BGR (BT.601 20-bit fixed point), the 11-bit horizontal pass and the VResizeLinear 32s->8u vertical pass, the u8
+//    result mapped through the per-channel normalisation LUT (fp32 out) and stored planar NCHW, or, for a tensor with
+//    layout = EVAM_LAYOUT_NHWC, as the slot's interleaved H x W x 3 image (a NHWC template parameter on the strip,
+//    band, wave and generic kernels: only the store epilogue differs). fp16 / bf16 output (EVAM_DTYPE_F16 / _BF16) is
+//    the same path with a table of 16-bit patterns and 2-byte stores (OUT = 2 on the generic, strip, ROI and wave
+//    kernels; interleaved 16-bit output: the generic kernel only).
+//  * The families differ in how source bytes reach the arithmetic: the generic and rows kernels gather taps straight
+//    from the frame through L1; the others stage source row segments in LDS by LDS-DMA, per workgroup (staged, roi) or
+//    per wave with counted vmcnt waits and no barrier in the loop (wave, strip, band). Each family's header says how.
+//  * Letterbox padding never touches the source. Nothing is MFMA-shaped: the path is HBM-bound integer gather work
+//    (roofline: HBM, 8 TB/s).
 //
-// One translation unit. This file: the seven kernel families, the kernel tables, launch_kernel and resident_per_cu
-// (HipKernels, the planner's HIP backend), HipRings, struct evam_pp, run_impl and the entry points. Included:
-// evam_params.h (kernel-argument structs) and evam_plan.h (the host planner), both HIP-free; the JPEG, JPEG-decode,
-// tracker and DetectionOutput kernels and entry points (evam_*_kernels.h, evam_*_api.h).
+// One translation unit. This file: the generic, rows, staged, wave and roi kernel families (each with the helpers only
+// it uses next to it), the kernel tables, launch_kernel and resident_per_cu (HipKernels, the planner's HIP backend),
+// HipRings, struct evam_pp, run_impl and the evam_pp_run entry points. Included:
+//  * evam_params.h (kernel-argument structs) and evam_plan.h (the host planner), both HIP-free;
+//  * evam_kernel_common.h (device helpers that two or more families share), evam_strip_kernels.h and
+//    evam_band_kernels.h (those two families, each with the helpers only it uses);
+//  * the device-resident ROI lists, JPEG, JPEG-decode, tracker and DetectionOutput kernels and entry points
+//    (evam_{rois,jpeg,jpeg_dec,track,detout}_kernels.h and _api.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,35 +66,13 @@ namespace {
 
 using namespace evam;
 
-// ------------------------------------------------------------------------------------------------
-// constants
-// ------------------------------------------------------------------------------------------------
-// Stage-removal diagnostics (bits: 2 no pixel math, 4 no stores, 8 loads only, 16 no loads, 32/64/128 stop
-// early). Compile-time only: a product build is 0, every diagnostic branch folds away, and no environment
-// setting can change results. A build with -DEVAM_PP_ABLATE=bits computes INVALID tensors; evam_pp_create
-// refuses it unless EVAM_PP_DIAGNOSTIC_BUILD_OK=1 (tools/prof_ablate.sh).
-#ifndef EVAM_PP_ABLATE
-#define EVAM_PP_ABLATE 0
-#endif
-constexpr int kAblate = EVAM_PP_ABLATE;
-// Cache-policy bits of the output stores: 2 = nt (non-temporal). The outputs are written once and
-// read by nobody in the launch; streaming them past the caches measured 1.5-3 % faster on C2/C3/C4
-// and 10 % on C5 (profiles/r02r_store_policy.txt). EVAM_PP_LOAD_AUX: the same bits for the LDS-DMA
-// source reads (A/B builds).
-#ifndef EVAM_PP_STORE_AUX
-#define EVAM_PP_STORE_AUX 2
-#endif
-#ifndef EVAM_PP_LOAD_AUX
-#define EVAM_PP_LOAD_AUX 0
-#endif
+}  // namespace
 
-// OpenCV color_yuv.simd.hpp ITUR_BT_601_*; the -128 chroma bias is folded into the constants.
-constexpr int kCY = 1220542, kCUB = 2116026, kCUG = -409993, kCVG = -852492, kCVR = 1673527;
-constexpr int kHalf = 1 << 19;
-constexpr int kKR = kHalf - 128 * kCVR - 16 * kCY;  // the luma term is max(Y,16)*CY (see yuv_to_bgr)
-constexpr int kKG = kHalf - 128 * kCVG - 128 * kCUG - 16 * kCY;
-constexpr int kKB = kHalf - 128 * kCUB - 16 * kCY;
+// Device code. evam_kernel_common.h and the family headers reopen the anonymous namespace at file scope, so a kernel's
+// symbol does not depend on where its text lives.
+#include "evam_kernel_common.h"
 
+namespace {
 
 // Workgroups are dispatched round-robin over the 8 XCDs (block b runs on XCD b % 8). Remap so each
 // XCD walks a contiguous run of tiles: neighbouring tiles of one frame share source rows at their
@@ -99,14 +81,6 @@ __device__ inline int xcd_tile(int b, int grid) {
     const int q = grid >> 3, r = grid & 7, x = b & 7, i = b >> 3;
     return x < r ? x * (q + 1) + i : r * (q + 1) + (x - r) * q + i;
 }
-
-// ------------------------------------------------------------------------------------------------
-// exact OpenCV arithmetic (shared host/device)
-// ------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t umulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
-
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
 
 // BT.601 20-bit fixed point (OpenCV uvToRGBuv + yRGBuvToRGBA). Arguments are raw bytes; every
 // product fits the full-rate 24-bit multiplier.
@@ -119,38 +93,6 @@ __device__ __forceinline__ void yuv_to_bgr(int Y, int U, int V, int& b, int& g, 
     g = clamp255((y + guv) >> 20);
     r = clamp255((y + ruv) >> 20);
 }
-
-// VResizeLinear<uchar,int,short,FixedPtCast<int,uchar,22>,VResizeLinearVec_32s8u>:
-//   dst = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2
-// evaluated on the full-rate 24-bit multiplier. The column table holds a' = a << 4 and the row table
-// b' = b << 8, so the horizontal pass yields D' = D << 4 (< 2^23) and
-//   (b * (D >> 4)) >> 16 == mulhi_u24(b', D' & ~0xFF)
-// exactly (b' * ((D >> 4) << 8) = b * (D >> 4) * 2^16).
-__device__ __forceinline__ uint32_t mulhi_u24(uint32_t a, uint32_t b) {
-    return (uint32_t)(((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu)) >> 32);
-}
-__device__ __forceinline__ int vresize(uint32_t D0s, uint32_t D1s, uint32_t b0s, uint32_t b1s) {
-    return (int)((mulhi_u24(b0s, D0s & 0xFFFF00u) + mulhi_u24(b1s, D1s & 0xFFFF00u) + 2u) >> 2);
-}
-// Same, for OUT != 0 returned as 4 * result (the byte offset into a LUT section of 4-byte entries).
-template <int OUT>
-__device__ __forceinline__ uint32_t vfinal(uint32_t D0s, uint32_t D1s, uint32_t b0s, uint32_t b1s) {
-    const uint32_t x = mulhi_u24(b0s, D0s & 0xFFFF00u) + mulhi_u24(b1s, D1s & 0xFFFF00u) + 2u;
-    return OUT != 0 ? (x & ~3u) : (x >> 2);
-}
-// Same, for horizontal results already masked with kVMask (a kernel that reuses a source row's results).
-constexpr uint32_t kVMask = 0xFFFF00u;
-template <int OUT>
-__device__ __forceinline__ uint32_t vfinal_masked(uint32_t D0m, uint32_t D1m, uint32_t b0s, uint32_t b1s) {
-    const uint32_t x = mulhi_u24(b0s, D0m) + mulhi_u24(b1s, D1m) + 2u;
-    return OUT != 0 ? (x & ~3u) : (x >> 2);
-}
-
-template <int FMT>
-struct FmtTraits {
-    static constexpr int bpp = FMT == kBGRX ? 4 : (FMT == kBGR ? 3 : 1);
-    static constexpr int nchroma = FMT == kNV12 ? 1 : (FMT == kI420 ? 2 : 0);
-};
 
 // Raw bytes of one source pixel, read straight from the frame (global memory, through L1/L2).
 // Plane bases are wave-uniform (SGPR) and offsets 32-bit, so each load is one saddr-form instruction.
@@ -184,51 +126,6 @@ __device__ __forceinline__ void to_bgr(const uint32_t (&v)[3], int& b, int& g, i
         b = v[0] & 0xFF; g = (v[0] >> 8) & 0xFF; r = (v[0] >> 16) & 0xFF;
     } else {
         b = (int)v[0]; g = (int)v[1]; r = (int)v[2];
-    }
-}
-
-// Planar stores of one pixel. Plane bases are wave-uniform (SGPR) and the offset is a 32-bit byte
-// offset, so every store is one saddr-form instruction with no 64-bit address arithmetic.
-// NHWC (interleaved output): d0 is the slot base and the pixel's three elements are adjacent at 3 * o
-// (d1, d2 unused); element stores only, so a slot may start at any element-aligned address.
-// OUT == 2: the 16-bit pattern in the low half of table entry i (fp16 / bf16 bits, no conversion on the device).
-__device__ __forceinline__ uint16_t lut_u16(const float* __restrict__ lut, int i) {
-    return *reinterpret_cast<const uint16_t*>(lut + i);
-}
-template <int OUT, bool NHWC = false>
-__device__ __forceinline__ void store_px(uint8_t* d0, uint8_t* d1, uint8_t* d2, const float* __restrict__ lut,
-                                         uint32_t o, int v0, int v1, int v2) {
-    if constexpr (NHWC) {
-        const uint32_t o3 = o * 3u;
-        if constexpr (OUT == 0) {
-            d0[o3] = (uint8_t)v0;
-            d0[o3 + 1] = (uint8_t)v1;
-            d0[o3 + 2] = (uint8_t)v2;
-        } else if constexpr (OUT == 2) {
-            uint16_t* const q = reinterpret_cast<uint16_t*>(d0 + (o3 << 1));
-            q[0] = lut_u16(lut, v0);
-            q[1] = lut_u16(lut, 256 + v1);
-            q[2] = lut_u16(lut, 512 + v2);
-        } else {
-            float* const q = reinterpret_cast<float*>(d0 + (o3 << 2));
-            q[0] = lut[v0];
-            q[1] = lut[256 + v1];
-            q[2] = lut[512 + v2];
-        }
-    } else if constexpr (OUT == 0) {
-        d0[o] = (uint8_t)v0;
-        d1[o] = (uint8_t)v1;
-        d2[o] = (uint8_t)v2;
-    } else if constexpr (OUT == 2) {
-        const uint32_t ob = o << 1;
-        *reinterpret_cast<uint16_t*>(d0 + ob) = lut_u16(lut, v0);
-        *reinterpret_cast<uint16_t*>(d1 + ob) = lut_u16(lut, 256 + v1);
-        *reinterpret_cast<uint16_t*>(d2 + ob) = lut_u16(lut, 512 + v2);
-    } else {
-        const uint32_t ob = o << 2;
-        *reinterpret_cast<float*>(d0 + ob) = lut[v0];
-        *reinterpret_cast<float*>(d1 + ob) = lut[256 + v1];
-        *reinterpret_cast<float*>(d2 + ob) = lut[512 + v2];
     }
 }
 
@@ -412,56 +309,6 @@ __device__ __forceinline__ void y_plus_uv(int Y, const UV3& t, int& b, int& g, i
     b = clamp255((y + t.b) >> 20);
     g = clamp255((y + t.g) >> 20);
     r = clamp255((y + t.r) >> 20);
-}
-
-// Saturating form of the same integers, two taps per register. The chroma terms carry the bias
-// 2^32 - 2^28 on top of kK*, so for S = y + term (the BT.601 sum before >> 20) the unsigned
-// saturating add y + term' is S + 2^32 - 2^28 when S < 2^28 and 0xFFFFFFFF otherwise; every term'
-// lies in [0, 2^32) (no wrap). Its high half is then floor(S / 2^16) + 61440, and one u16
-// saturating subtract of 61440 clamps it to [0, 4095], i.e. to 16 * clamp255(S >> 20) plus four
-// low bits that a mask drops. Two taps' high halves share one register (v_perm), so the clamp costs
-// a packed subtract and a mask per tap pair, and the horizontal pass D = c0*a0 + c1*a1 is one
-// v_dot2_u32_u16 that yields 16 * D, the D' vresize takes. tools/check_sat_clamp.py checks the
-// clamp against clamp255((y + term) >> 20) over all 2^24 (Y, U, V).
-typedef unsigned short evam_u16x2 __attribute__((ext_vector_type(2)));
-constexpr uint32_t kSatBias = 0xF0000000u;  // 2^32 - 2^28
-constexpr uint32_t kKBs = (uint32_t)kKB + kSatBias, kKGs = (uint32_t)kKG + kSatBias, kKRs = (uint32_t)kKR + kSatBias;
-struct UVs { uint32_t b, g, r; };
-__device__ __forceinline__ UVs uv_terms_sat(uint32_t U, uint32_t V) {
-    // G as two chained v_mad_i32_i24 (the opaque middle value keeps the compiler from re-forming two products and
-    // an add3): 4 VALU per chroma sample instead of 5
-    int gu = __mul24((int)U, kCUG) + (int)kKGs;
-    asm("" : "+v"(gu));
-    return UVs{__umul24(U, (uint32_t)kCUB) + kKBs, (uint32_t)(__mul24((int)V, kCVG) + gu), __umul24(V, (uint32_t)kCVR) + kKRs};
-}
-__device__ __forceinline__ uint32_t luma_term(uint32_t Y) { return __umul24(max(Y, 16u), (uint32_t)kCY); }
-// One source row, one channel: taps' sums s0 (column x0) and s1 (column x1), packed weights w = a0 | a1 << 16
-// (plain 11-bit) -> 16 * (c0 * a0 + c1 * a1).
-// hpass_sums: the same from the taps' saturated sums (pixels whose taps meet at one column share a sum).
-__device__ __forceinline__ uint32_t hpass_sums(uint32_t s0, uint32_t s1, uint32_t w) {
-    const evam_u16x2 h = __builtin_bit_cast(evam_u16x2, __builtin_amdgcn_perm(s1, s0, 0x07060302u));
-    const evam_u16x2 c = __builtin_elementwise_sub_sat(h, (evam_u16x2){61440, 61440});
-    const uint32_t c16 = __builtin_bit_cast(uint32_t, c) & 0xFFF0FFF0u;
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(evam_u16x2, c16), __builtin_bit_cast(evam_u16x2, w), 0u, false);
-}
-__device__ __forceinline__ uint32_t hpass_sat(uint32_t y0, uint32_t t0, uint32_t y1, uint32_t t1, uint32_t w) {
-    return hpass_sums(__builtin_elementwise_add_sat(y0, t0), __builtin_elementwise_add_sat(y1, t1), w);
-}
-// u8 bytes (x >> 2) of four vertical-pass sums x = mulhi + mulhi + 2 < 2^16 (each result <= 255), packed little-endian: two u16 pairs, one packed
-// shift each, one byte permute (5 VALU for 4 pixels instead of 4 shifts and 4 shift / or steps)
-__device__ __forceinline__ uint32_t pack4_u8_sums(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3) {
-    const evam_u16x2 p01 = __builtin_bit_cast(evam_u16x2, x0 | (x1 << 16)) >> (evam_u16x2){2, 2};
-    const evam_u16x2 p23 = __builtin_bit_cast(evam_u16x2, x2 | (x3 << 16)) >> (evam_u16x2){2, 2};
-    return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, p23), __builtin_bit_cast(uint32_t, p01), 0x06040200u);
-}
-
-// Horizontal pass of one source row, three channels, from the two taps' luma bytes and chroma terms.
-__device__ __forceinline__ void hrow_sat(uint32_t Y0, uint32_t Y1, const UVs& tA, const UVs& tB, uint32_t w,
-                                         uint32_t (&H)[3]) {
-    const uint32_t yA = luma_term(Y0), yB = luma_term(Y1);
-    H[0] = hpass_sat(yA, tA.b, yB, tB.b, w);
-    H[1] = hpass_sat(yA, tA.g, yB, tB.g, w);
-    H[2] = hpass_sat(yA, tA.r, yB, tB.r, w);
 }
 
 template <int FMT>
@@ -688,30 +535,6 @@ __global__ __launch_bounds__(kThreads) void evam_pp_rows(const RParams P) {
     }
 }
 
-// Row table of up to 64 consecutive output rows held one row per lane (r0, r1, b0, b1 in four VGPRs),
-// read back as wave-uniform values with v_readlane: the per-row lookups of the staging loops then cost
-// no scalar-memory round trip (a dependent s_load per row serialised the DMA issue).
-struct LaneRows {
-    int r0, r1, b0, b1;
-    __device__ __forceinline__ void load(const YTab* ytab, int Ybase, int n, int lane) {
-        const int Y = Ybase + (lane < n ? lane : 0);
-        const YTab e = ytab[Y];
-        r0 = e.r0; r1 = e.r1; b0 = e.b0; b1 = e.b1;
-    }
-    __device__ __forceinline__ int R0(int i) const { return __builtin_amdgcn_readlane(r0, i); }
-    __device__ __forceinline__ int R1(int i) const { return __builtin_amdgcn_readlane(r1, i); }
-    __device__ __forceinline__ int B0(int i) const { return __builtin_amdgcn_readlane(b0, i); }
-    __device__ __forceinline__ int B1(int i) const { return __builtin_amdgcn_readlane(b1, i); }
-};
-
-// Workgroup barrier for data written to LDS by ds_write only: lgkmcnt(0) and a raw s_barrier. __syncthreads()
-// also waits vmcnt(0), which drains every LDS-DMA in flight (cdna_hip_programming.md, Pipelining across barriers).
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 __device__ __forceinline__ void vmcnt_at_most(int n) {
     n = __builtin_amdgcn_readfirstlane(n);
     if (n >= 24) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
@@ -719,19 +542,6 @@ __device__ __forceinline__ void vmcnt_at_most(int n) {
     else if (n >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else if (n >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// Same, exact for n <= 24 (a jump over immediates; larger n waits for 24).
-__device__ __forceinline__ void vmcnt_exact(int n) {
-    n = __builtin_amdgcn_readfirstlane(n);
-#define EVAM_VMC(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n) {
-        EVAM_VMC(0) EVAM_VMC(1) EVAM_VMC(2) EVAM_VMC(3) EVAM_VMC(4) EVAM_VMC(5) EVAM_VMC(6) EVAM_VMC(7) EVAM_VMC(8)
-        EVAM_VMC(9) EVAM_VMC(10) EVAM_VMC(11) EVAM_VMC(12) EVAM_VMC(13) EVAM_VMC(14) EVAM_VMC(15) EVAM_VMC(16)
-        EVAM_VMC(17) EVAM_VMC(18) EVAM_VMC(19) EVAM_VMC(20) EVAM_VMC(21) EVAM_VMC(22) EVAM_VMC(23)
-        default: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    }
-#undef EVAM_VMC
 }
 
 // Staged uniform-geometry kernel. A workgroup owns a TW x TH tile (TW = 64 x NSEGX) and walks it in
@@ -1118,10 +928,6 @@ __global__ __launch_bounds__(kThreads) void evam_pp_staged(const SParams P) {
 // wave-row kernel (uniform geometry)
 // ------------------------------------------------------------------------------------------------
 
-typedef int evam_v2i __attribute__((ext_vector_type(2)));
-typedef int evam_v3i __attribute__((ext_vector_type(3)));
-typedef int evam_v4i __attribute__((ext_vector_type(4)));
-
 // PX adjacent output pixels of one channel from one lane: a single buffer store of PX x 4 bytes (fp32),
 // PX x 2 bytes (fp16 / bf16) or PX bytes (u8). lut == nullptr: u8 output.
 template <int OUT, int PX>
@@ -1158,44 +964,6 @@ __device__ __forceinline__ void store_vec(const __amdgpu_buffer_rsrc_t rs, uint3
             __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(v[0] | (v[1] << 8)), rs, vo, so, EVAM_PP_STORE_AUX);
         else
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v[0], rs, vo, so, EVAM_PP_STORE_AUX);
-    }
-}
-
-// Same, with the fp32 values given as byte offsets into an LDS LUT section `lb` (vfinal<1>): the LUT
-// read needs no address arithmetic (section base 0, 1024, 2048 is the instruction's immediate offset).
-template <int OUT, int PX>
-__device__ __forceinline__ void store_off(const __amdgpu_buffer_rsrc_t rs, uint32_t vo, const uint8_t* lb,
-                                          const uint32_t (&v)[PX]) {
-    if constexpr (OUT == 1) {
-        auto L = [&](uint32_t o) { return (int)*reinterpret_cast<const uint32_t*>(lb + o); };
-        if constexpr (PX == 4) {
-            evam_v4i q = {L(v[0]), L(v[1]), L(v[2]), L(v[3])};
-            __builtin_amdgcn_raw_buffer_store_b128(q, rs, vo, 0, EVAM_PP_STORE_AUX);
-        } else if constexpr (PX == 2) {
-            evam_v2i q = {L(v[0]), L(v[1])};
-            __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, 0, EVAM_PP_STORE_AUX);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b32((uint32_t)L(v[0]), rs, vo, 0, EVAM_PP_STORE_AUX);
-        }
-    } else if constexpr (OUT == 2) {
-        // the low u16 of each 4-byte entry, two per dword (see store_vec)
-        auto H = [&](uint32_t o) { return (uint32_t)*reinterpret_cast<const uint16_t*>(lb + o); };
-        if constexpr (PX == 4) {
-            evam_v2i q = {(int)(H(v[0]) | (H(v[1]) << 16)), (int)(H(v[2]) | (H(v[3]) << 16))};
-            __builtin_amdgcn_raw_buffer_store_b64(q, rs, vo, 0, EVAM_PP_STORE_AUX);
-        } else if constexpr (PX == 2) {
-            __builtin_amdgcn_raw_buffer_store_b32(H(v[0]) | (H(v[1]) << 16), rs, vo, 0, EVAM_PP_STORE_AUX);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)H(v[0]), rs, vo, 0, EVAM_PP_STORE_AUX);
-        }
-    } else {
-        if constexpr (PX == 4)
-            __builtin_amdgcn_raw_buffer_store_b32(v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24), rs, vo, 0,
-                                                  EVAM_PP_STORE_AUX);
-        else if constexpr (PX == 2)
-            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)(v[0] | (v[1] << 8)), rs, vo, 0, EVAM_PP_STORE_AUX);
-        else
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v[0], rs, vo, 0, EVAM_PP_STORE_AUX);
     }
 }
 
@@ -1519,1013 +1287,12 @@ __global__ __launch_bounds__(kThreads) void evam_pp_wave(const WParams P) {
     }
 }
 
-// Diagnostic builds only (-DEVAM_PP_TRACE): timestamps of the 100 MHz constant clock written by lane 0
-// with a vector store, per workgroup (EVAM_STAMP: the ROI kernel, tools/roi_timeline.py) or per wave
-// (EVAM_WSTAMP: the strip kernel, tools/wave_timeline.py). Product builds compile no stamp. In the strip
-// kernel a stamp is one more VMEM operation than its counted waits assume, which only makes them wait
-// longer (still exact data, slightly perturbed timing).
-#ifdef EVAM_PP_TRACE
-constexpr int kTraceWGs = 16384, kTraceSlots = 12;
-__device__ unsigned long long g_evam_trace[kTraceWGs * kTraceSlots];
-#define EVAM_STAMP(k)                                                                                  \
-    do {                                                                                               \
-        unsigned long long t_;                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-        if (threadIdx.x == 0 && blockIdx.x < kTraceWGs) g_evam_trace[blockIdx.x * kTraceSlots + (k)] = t_; \
-    } while (0)
-#define EVAM_TRACE_VAL(k, v)                                                                           \
-    do {                                                                                               \
-        if (threadIdx.x == 0 && blockIdx.x < kTraceWGs) g_evam_trace[blockIdx.x * kTraceSlots + (k)] = (v); \
-    } while (0)
-#define EVAM_WSTAMP(k)                                                                                 \
-    do {                                                                                               \
-        unsigned long long t_;                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");               \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-        const unsigned w_ = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); \
-        if ((threadIdx.x & 63) == 0 && w_ < (unsigned)kTraceWGs) g_evam_trace[w_ * kTraceSlots + (k)] = t_; \
-    } while (0)
-#define EVAM_WTRACE_VAL(k, v)                                                                          \
-    do {                                                                                               \
-        const unsigned w_ = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); \
-        if ((threadIdx.x & 63) == 0 && w_ < (unsigned)kTraceWGs) g_evam_trace[w_ * kTraceSlots + (k)] = (v); \
-    } while (0)
-#else
-#define EVAM_STAMP(k) do { } while (0)
-#define EVAM_TRACE_VAL(k, v) do { } while (0)
-#define EVAM_WSTAMP(k) do { } while (0)
-#define EVAM_WTRACE_VAL(k, v) do { } while (0)
-#endif
+}  // namespace
 
-struct RecFrame { __m128i l[3]; };  // a record's bytes 0-47 for one source (bytes 40-47 zero)
+#include "evam_strip_kernels.h"
+#include "evam_band_kernels.h"
 
-// ------------------------------------------------------------------------------------------------
-// strip kernel (uniform geometry, 4:2:0 sources, no shared source rows between output rows)
-// ------------------------------------------------------------------------------------------------
-
-// Row-strip kernel for uniform-geometry 4:2:0 batches whose output rows do not share source rows
-// (downscales: C2, C4, C5). Every wave owns one strip of 64 x PX output columns of a tile (lane l holds
-// columns l, l + 64, ...) and walks the tile's rows alone, one output row per step, with no workgroup
-// barrier after the prologue:
-//  * a ring of D row entries per wave (two luma row segments, one or two chroma row segments: the strip's
-//    16-byte-aligned footprint) fed by LDS-DMA D rows ahead; the wait for a row is one counted vmcnt,
-//    so the ring's other rows and the stores of the previous rows stay in flight;
-//  * the OpenCV coefficient tables of the strip's columns (per lane) and of the tile's rows (one per
-//    lane, read back with v_readlane) are computed in the prologue by the kernels' shared linear_coef, so
-//    the first DMA waits for no table load;
-//  * per pixel: four luma taps and two chroma taps per chroma row from LDS, BT.601 as saturating two-tap
-//    registers, the 11-bit horizontal pass as one v_dot2 per channel, VResizeLinear 32s->8u as mulhi_u24,
-//    the LUT (fp32) and three planar stores (256 contiguous bytes per store instruction).
-// Strip width: the C2 data movement alone takes 39.4 us in 64-column strips and 36.4 us in 128-column
-// strips (one 480-byte DMA segment per source row instead of 240: half the DMA instructions for the same
-// bytes), the copy floor of those bytes on the same box (profiles/r03c_strip_bw.txt).
-// Letterbox rows are plain fill stores outside the ring; letterbox columns are a per-lane select in the
-// strips that have any. D = ring depth (rows of DMA in flight).
-// Progress-based priority (EVAM_PP_PRIO): s_setprio 3 at the start, one level lower at each quarter of a wave's n
-// steps (rows or row groups), so the waves behind get the issue slot when several are ready. One scalar compare per
-// step against the next threshold; the level change sits in the rarely taken branch (the three-way compare chain it
-// replaces cost six scalar instructions per step).
-struct ProgressPrio {
-    int next, q2, q3, level;
-    __device__ __forceinline__ ProgressPrio(bool on, int n) : next(on ? n / 4 : -1), q2(n / 2), q3((3 * n) / 4), level(3) {
-        if (on) __builtin_amdgcn_s_setprio(3);
-    }
-    __device__ __forceinline__ void step(int i) {
-        if (__builtin_expect(i != next, 1)) return;
-        if (level == 3) {
-            __builtin_amdgcn_s_setprio(2);
-            level = 2;
-            next = q2;
-        } else if (level == 2) {
-            __builtin_amdgcn_s_setprio(1);
-            level = 1;
-            next = q3;
-        } else {
-            __builtin_amdgcn_s_setprio(0);
-            level = 0;
-            next = -1;
-        }
-    }
-};
-
-// NHWC (interleaved fp32 output): a pixel's three values leave as one 12-byte store, so a store instruction covers
-// 768 contiguous bytes of the row where the planar one covers 256 in each of three planes, and a row costs one
-// store per pixel column group instead of three. (u8 would be 3-byte stores per lane: the wave kernel serves it.)
-template <int FMT, int OUT, int D, int PX, int PR, bool NHWC = false>
-__global__ __launch_bounds__(512) void evam_pp_strip(const TParams P) {
-    static_assert(!NHWC || OUT == 1, "the interleaved strip store is fp32 only");
-    constexpr int NS = NHWC ? 1 : 3;  // stores per pixel column group and row
-    // the LUT at a static LDS address (folds into the reads' immediate offsets); the rings after it
-    __shared__ __attribute__((aligned(16))) float lut_s[OUT != 0 ? 768 : 4];
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    static_assert(FMT == kNV12 || FMT == kI420 || FMT == kBGRX, "4:2:0 or BGRx sources");
-    static_assert(D >= 1 && D <= 4, "ring depth");
-    static_assert(PX == 1 || PX == 2, "pixels per lane");
-    constexpr int SLOT = strip_slot(FMT, PX);
-    constexpr bool PK = FMT == kBGRX;                 // packed BGRx: one plane, 4 bytes a pixel, no conversion
-    constexpr int NPC = FMT == kI420 ? 2 : (PK ? 0 : 1);  // chroma planes
-    // PR (paired taps): both source rows of a plane go out in ONE LDS-DMA instruction, lanes 0-31 the first
-    // row's chunks and lanes 32-63 the second's (I420: U tap0 / U tap1 / V tap0 / V tap1 in lane quarters), so
-    // every row costs exactly NI instructions. Without PR a row costs 2 + NPC (chroma row shared) or 2 + 2 NPC.
-    static_assert(PR == 0 || PR == 1, "paired taps");
-    constexpr int NMIN = PR ? (PK ? 1 : 2) : 2 + NPC;  // fewest DMA instructions of one row (PR: exact)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (kAblate & 128) return;  // diagnostics: launch cost only
-    EVAM_WSTAMP(0);
-    const uint8_t *p0, *p1, *p2;
-    int pitch0, pitch1, pitch2, x0, y0, index, p_nw, p_DH, p_DW, strip, Y0, Y1;
-    int g_ox, g_rw, g_oy, g_rh, g_cw, k_ch, k_rgb;
-    double k_scale_x, k_scale_y;
-    const float* k_lut;
-    ColSpan sf;
-    // grid (tile column, tile row, item): every kernel-argument load of the prologue has an address known at
-    // entry, so they all go out in one batch (one round trip before the first DMA)
-    const int item = blockIdx.z, ty = blockIdx.y;
-    const ItemArg& it = P.items[item];
-    sf = P.sfoot[min((int)blockIdx.x * 8 + wave, kSfoot - 1)];
-    const int p_TH = P.TH;
-    p_nw = P.nw; p_DH = P.DH; p_DW = P.DW;
-    p0 = it.plane[0];
-    p1 = it.plane[1];
-    p2 = it.plane[2];
-    pitch0 = it.pitch[0]; pitch1 = it.pitch[1]; pitch2 = it.pitch[2];
-    x0 = it.x0; y0 = it.y0;
-    index = it.index;
-    asm volatile("" ::"s"(p_nw), "s"(p_TH), "s"(p_DH), "s"(p_DW), "s"(P.ox), "s"(P.rw), "s"(P.oy), "s"(P.rh),
-                 "s"(P.wave_bytes), "s"(p0), "s"(p1), "s"(p2), "s"(pitch0), "s"(pitch1), "s"(pitch2), "s"(x0), "s"(y0),
-                 "s"(index), "s"(sf.x), "s"(sf.y), "s"(P.dst), "s"(P.slot_offset), "s"(P.slot_stride));
-    // the row table's and the LUT DMA's parameters in the same batch, as opaque values the compiler cannot
-    // reload: loaded where first used, they were one or two more dependent kernel-argument round trips before
-    // the first DMA
-    k_scale_y = P.scale_y;
-    k_ch = P.ch; k_rgb = P.color_rgb;
-    k_lut = P.lut;
-    asm volatile("" : "+s"(k_scale_y), "+s"(k_ch), "+s"(k_lut), "+s"(k_rgb));
-    strip = (int)blockIdx.x * p_nw + wave;
-    Y0 = ty * p_TH; Y1 = min(Y0 + p_TH, p_DH);
-    g_ox = P.ox; g_rw = P.rw; g_oy = P.oy; g_rh = P.rh; g_cw = P.cw;
-    k_scale_x = P.scale_x;
-    const int X0 = strip * 64 * PX;
-    const bool live = X0 < p_DW;  // a wave past the last strip only joins the LUT barrier
-    const bool cols = live && sf.x >= 0;
-    int fsY = 0, nY = 0, fsC = 0, nC = 0;
-    if (cols) footprint_chunks(FMT, PK ? 4 : 1, x0 + sf.x, x0 + sf.y, fsY, nY, fsC, nC);
-    // visible output rows of the tile (the rest are letterbox fill)
-    const int vr0 = max(Y0, g_oy), vr1 = min(Y1, g_oy + g_rh);
-    const int n = cols && vr1 > vr0 ? vr1 - vr0 : 0;
-
-    // row table, one visible row per lane: source rows relative to the crop, weights << 8
-    int lr0 = 0, lr1 = 0, lb0 = 0, lb1 = 0;
-    if (lane < n) {
-        int sy, b0, b1;
-        linear_coef(vr0 + lane - g_oy, k_scale_y, k_ch, false, sy, b0, b1);
-        lr0 = min(max(sy, 0), k_ch - 1);
-        lr1 = min(max(sy + 1, 0), k_ch - 1);
-        lb0 = b0 << 8;
-        lb1 = b1 << 8;
-    }
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p0, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc((void*)p1, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)(NPC == 2 ? p2 : p1), (short)0, 0x7FFFFFFF, 0x00020000);
-    uint8_t* const wbuf = smem + wave * P.wave_bytes;
-    // Ring entry layout. Without PR: [Y tap0][Y tap1][C tap0][C tap1] (+ [V tap0][V tap1] for I420), SLOT bytes
-    // each; BGRx: [row tap0][row tap1]. With PR: [Y tap0 | Y tap1] (512 B halves) then, for 4:2:0,
-    // [C tap0 | C tap1] (NV12, 512 B halves) or [U tap0 | U tap1 | V tap0 | V tap1] (I420, 256 B quarters).
-    //   SY: Y tap1 - Y tap0; CB: chroma region; SC: C tap1 - C tap0; SV: I420 V tap0 - U tap0.
-    constexpr int SY = PR ? 512 : SLOT;
-    constexpr int CB = PR ? 1024 : 2 * SLOT;
-    constexpr int SC = PR ? (NPC == 2 ? 256 : 512) : SLOT;
-    constexpr int SV = PR ? 512 : 2 * SLOT;
-    constexpr int GRP = PR ? (PK ? 1024 : 2048) : 2 * SLOT + 2 * NPC * SLOT;
-    constexpr int segY = SY;
-    // I420 with PR: one buffer resource over both chroma planes, based at the lower one. Every byte read lies below
-    // (offset of the upper plane) + (its extent), which must stay under num_records 0x7FFFFFFF: the host admits the
-    // pairing only when that holds for every item of the launch, else the group runs unpaired
-    const uint8_t* const pcl = NPC == 2 && PR ? (p1 < p2 ? p1 : p2) : p1;
-    const uint32_t dU = (uint32_t)(p1 - pcl), dV = (uint32_t)(p2 - pcl);
-    const __amdgpu_buffer_rsrc_t rsC2 = __builtin_amdgcn_make_buffer_rsrc((void*)pcl, (short)0, 0x7FFFFFFF, 0x00020000);
-    auto issue = [&](int i, int k) {
-        if (kAblate & 16) return;  // diagnostics: no DMA
-        const int ya = y0 + __builtin_amdgcn_readlane(lr0, i), yb = y0 + __builtin_amdgcn_readlane(lr1, i);
-        uint8_t* e = wbuf + k * GRP;
-        if constexpr (PR) {
-            const int hi = lane >> 5, c = lane & 31;
-            if (c < nY)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsY, (__attribute__((address_space(3))) void*)e, 16,
-                                                         (uint32_t)((hi ? yb : ya) * pitch0 + fsY + c * 16), 0,
-                                                         EVAM_PP_LOAD_AUX, 0);
-            if constexpr (NPC == 1) {
-                const int ca = ya >> 1, cb = yb >> 1;
-                if (c < nC && (!hi || ca != cb))
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsU, (__attribute__((address_space(3))) void*)(e + CB), 16,
-                                                             (uint32_t)((hi ? cb : ca) * pitch1 + fsC + c * 16), 0,
-                                                             EVAM_PP_LOAD_AUX, 0);
-            } else if constexpr (NPC == 2) {
-                const int ca = ya >> 1, cb = yb >> 1, q = lane >> 4, c4 = lane & 15, r = (q & 1) ? cb : ca;
-                const uint32_t off = (q & 2) ? dV + (uint32_t)(r * pitch2) : dU + (uint32_t)(r * pitch1);
-                if (c4 < nC && (!(q & 1) || ca != cb))
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsC2, (__attribute__((address_space(3))) void*)(e + CB), 16,
-                                                             off + (uint32_t)(fsC + c4 * 16), 0, EVAM_PP_LOAD_AUX, 0);
-            }
-            return;
-        }
-        const uint32_t vo = (uint32_t)lane * 16u;
-        if (lane < nY) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsY, (__attribute__((address_space(3))) void*)e, 16, vo,
-                                                     ya * pitch0 + fsY, EVAM_PP_LOAD_AUX, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsY, (__attribute__((address_space(3))) void*)(e + segY), 16, vo,
-                                                     yb * pitch0 + fsY, EVAM_PP_LOAD_AUX, 0);
-        }
-        if constexpr (NPC == 0) return;
-        const int ca = ya >> 1, cb = yb >> 1;
-        if (lane < nC) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsU, (__attribute__((address_space(3))) void*)(e + CB), 16, vo,
-                                                     ca * pitch1 + fsC, EVAM_PP_LOAD_AUX, 0);
-            if constexpr (NPC == 2)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (__attribute__((address_space(3))) void*)(e + CB + SV),
-                                                         16, vo, ca * pitch2 + fsC, EVAM_PP_LOAD_AUX, 0);
-        }
-        if (ca != cb && lane < nC) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsU, (__attribute__((address_space(3))) void*)(e + CB + SC), 16,
-                                                     vo, cb * pitch1 + fsC, EVAM_PP_LOAD_AUX, 0);
-            if constexpr (NPC == 2)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (__attribute__((address_space(3))) void*)(e + CB + SV + SC),
-                                                         16, vo, cb * pitch2 + fsC, EVAM_PP_LOAD_AUX, 0);
-        }
-    };
-
-    // The LUT first (oldest VMEM: the first row's wait covers it), then the ring's first D rows. With four or
-    // more waves, waves 0-2 each bring one 1 KB section by LDS-DMA (source section swapped for RGB): no ds_write
-    // follows the ring's DMA, so nothing makes the compiler drain the ring before the LUT barrier.
-    const int nthr = p_nw * 64;
-    const bool lut_early = nthr >= 256;
-    if constexpr (OUT != 0) {
-        if (lut_early && wave < 3) {
-            const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void*)k_lut, (short)0, 3072, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsL, (__attribute__((address_space(3))) void*)(lut_s + wave * 256), 16,
-                                                     (uint32_t)lane * 16u, (k_rgb ? 2 - wave : wave) * 1024, 0, 0);
-        }
-    }
-    const int npro = min(n, D);
-    for (int i = 0; i < npro; i++) issue(i, i);
-    EVAM_WSTAMP(1);
-    EVAM_WTRACE_VAL(5, (unsigned long long)blockIdx.z | ((unsigned long long)strip << 16) |
-                           ((unsigned long long)blockIdx.y << 32) | ((unsigned long long)n << 48));
-
-    // per-lane column state of the lane's PX pixels: tap offsets inside the staged segments, packed
-    // 11-bit weights, store offsets
-    bool xin[PX], padc[PX];
-    uint32_t lY[PX], lC0[PX], lC1[PX], wp[PX], vo[PX];
-    bool anyp = false;
-    const size_t esz = out_esz(OUT);
-#pragma unroll
-    for (int j = 0; j < PX; j++) {
-        const int X = X0 + lane + 64 * j;
-        xin[j] = live && X < p_DW;
-        vo[j] = (uint32_t)(xin[j] ? X : 0) * (uint32_t)(NHWC ? 3 * esz : esz);
-        lY[j] = lC0[j] = lC1[j] = wp[j] = 0;
-        padc[j] = true;
-        const int dx = X - g_ox;
-        if (cols && xin[j] && dx >= 0 && dx < g_rw) {
-            int s0, a0, a1;
-            linear_coef(dx, k_scale_x, g_cw, true, s0, a0, a1);
-            const int ca = x0 + s0;  // tap 1 reads ca + 1: at the right edge (s0 = cw - 1) its weight a1 is 0
-            lY[j] = (uint32_t)(ca * (PK ? 4 : 1) - fsY);
-            if constexpr (FMT == kNV12) {
-                lC0[j] = (uint32_t)(2 * (ca >> 1) - fsC);
-                lC1[j] = (uint32_t)(2 * ((ca + 1) >> 1) - fsC);
-            } else if constexpr (FMT == kI420) {
-                lC0[j] = (uint32_t)((ca >> 1) - fsC);
-                lC1[j] = (uint32_t)(((ca + 1) >> 1) - fsC);
-            }
-            // BGRx: the weights carry the 16x that the 4:2:0 path's saturating clamp leaves on its taps
-            wp[j] = PK ? ((uint32_t)a0 << 4) | ((uint32_t)a1 << 20) : (uint32_t)a0 | ((uint32_t)a1 << 16);
-            padc[j] = false;
-        }
-        anyp |= xin[j] && padc[j];
-    }
-    // some visible lane shows letterbox columns (wave-uniform): only then the per-pixel fill select
-    const bool anypad = cols && __builtin_amdgcn_ballot_w64(anyp) != 0;
-    // stores per row of this wave: 3 per pixel column group with any lane inside the output (counted waits)
-    const bool full = X0 + 64 * (PX - 1) < p_DW;
-
-    const size_t plane = (size_t)p_DW * p_DH;
-    uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)(P.slot_offset + index * P.slot_stride) * 3 * plane * esz;
-    uint8_t* const d1 = d0 + plane * esz;
-    uint8_t* const d2 = d1 + plane * esz;
-    // output planes in source channel order (B, G, R): planes 0 and 2 exchanged for RGB; NHWC: rsO0 is the whole slot
-    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(!NHWC && k_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsO1 = __builtin_amdgcn_make_buffer_rsrc((void*)d1, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsO2 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d0 : d2), (short)0, 0x7FFFFFFF, 0x00020000);
-    // fill in source channel order (P.fill is in output plane order)
-    const uint32_t fq0 = P.fill & 0xFF, fq1 = (P.fill >> 8) & 0xFF, fq2 = (P.fill >> 16) & 0xFF;
-    const uint32_t fsh = OUT != 0 ? 2 : 0;
-    const uint32_t fill0 = (k_rgb ? fq2 : fq0) << fsh, fill1 = fq1 << fsh, fill2 = (k_rgb ? fq0 : fq2) << fsh;
-
-    if constexpr (OUT != 0) {
-        if (lut_early) {
-            // this wave's LUT section landed once at most the ring's DMA instructions are outstanding; the
-            // barrier then needs no vmcnt(0): each wave waits for its own ring rows in the loop
-            if (npro == D) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NMIN * D) : "memory");
-            else vmcnt_exact(NMIN * npro);
-            lds_barrier();
-        } else {  // workgroups of 1-3 waves (outputs narrower than 64 x PX x 3 + 1 columns)
-            for (int idx = threadIdx.x; idx < 768; idx += nthr)
-                lut_s[idx] = k_lut[k_rgb ? 512 - (idx & ~255) + (idx & 255) : idx];
-            __syncthreads();
-        }
-    }
-    EVAM_WSTAMP(2);
-    if (!live) return;
-    if (kAblate & 64) {  // diagnostics: prologue only (tables, LUT, the ring's first DMA)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("" ::"v"(lY[0]), "v"(lC0[0]), "v"(lC1[0]), "v"(wp[0]), "v"(vo[0]), "v"(lb0), "v"(lb1));
-        return;
-    }
-    const uint8_t* lutb = reinterpret_cast<const uint8_t*>(lut_s);
-    // per-lane LDS addresses of the taps in ring entry 0 (entry k adds k * GRP, an immediate offset)
-    const uint8_t* aY[PX];
-    const uint8_t* aC0[PX];
-    const uint8_t* aC1[PX];
-#pragma unroll
-    for (int j = 0; j < PX; j++) {
-        aY[j] = wbuf + lY[j];
-        aC0[j] = wbuf + CB + lC0[j];
-        aC1[j] = wbuf + CB + lC1[j];
-    }
-    // BT.601 chroma-term constants: the additive ones in VGPRs so every term is one v_mad (a VOP3 reads one
-    // scalar operand: the multiplier)
-    uint32_t kb = kKBs, kg = kKGs, kr = kKRs;
-    int cvg = kCVG, cug = kCUG;
-    asm volatile("" : "+v"(kb), "+v"(kg), "+v"(kr), "+s"(cvg), "+s"(cug));
-    auto uvt = [&](uint32_t U, uint32_t V) {
-        // g = V * CVG + (U * CUG + K): two v_mad_i32_i24 (the sum of two products would select mul, mul, add3)
-        int gu = __mul24((int)U, cug) + (int)kg;
-        asm("" : "+v"(gu));  // keeps the association (no asm volatile: still scheduled freely)
-        return UVs{__umul24(U, (uint32_t)kCUB) + kb, (uint32_t)(__mul24((int)V, cvg) + gu), __umul24(V, (uint32_t)kCVR) + kr};
-    };
-    // pixel column group j of row Y; v: LUT byte offsets (fp32) or bytes (u8), source channel order
-    auto put = [&](int Y, int j, uint32_t v0, uint32_t v1, uint32_t v2) {
-        if (!xin[j]) return;
-        if (kAblate & 4) {  // diagnostics: no stores
-            asm volatile("" ::"v"(v0), "v"(v1), "v"(v2));
-            return;
-        }
-        if constexpr (NHWC) {
-            // the LUT sections are in source channel order (loaded swapped for RGB), the store in output order; the
-            // row offset goes in the VGPR offset (soffset 0: the store-data hazard of wide stores, see evam_pp_wave)
-            const int l0 = (int)*reinterpret_cast<const uint32_t*>(lutb + v0);
-            const int l1 = (int)*reinterpret_cast<const uint32_t*>(lutb + 1024 + v1);
-            const int l2 = (int)*reinterpret_cast<const uint32_t*>(lutb + 2048 + v2);
-            const evam_v3i q = {k_rgb ? l2 : l0, l1, k_rgb ? l0 : l2};
-            __builtin_amdgcn_raw_buffer_store_b96(q, rsO0, vo[j] + (uint32_t)(Y * p_DW) * 12u, 0, EVAM_PP_STORE_AUX);
-            return;
-        }
-        const int so = (int)((uint32_t)(Y * p_DW) * (uint32_t)esz);
-        if constexpr (OUT == 1) {
-            __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + v0), rsO0, vo[j], so, EVAM_PP_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + 1024 + v1), rsO1, vo[j], so, EVAM_PP_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b32(*reinterpret_cast<const uint32_t*>(lutb + 2048 + v2), rsO2, vo[j], so, EVAM_PP_STORE_AUX);
-        } else if constexpr (OUT == 2) {
-            // the low u16 of the entry: lane l holds columns l, l + 64, so a store instruction covers 128 contiguous bytes
-            __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const uint16_t*>(lutb + v0), rsO0, vo[j], so, EVAM_PP_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const uint16_t*>(lutb + 1024 + v1), rsO1, vo[j], so, EVAM_PP_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const uint16_t*>(lutb + 2048 + v2), rsO2, vo[j], so, EVAM_PP_STORE_AUX);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v0, rsO0, vo[j], so, EVAM_PP_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v1, rsO1, vo[j], so, EVAM_PP_STORE_AUX);
-            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v2, rsO2, vo[j], so, EVAM_PP_STORE_AUX);
-        }
-    };
-    auto put_fill = [&](int Y) {
-#pragma unroll
-        for (int j = 0; j < PX; j++) put(Y, j, fill0, fill1, fill2);
-    };
-    // letterbox rows above the ring: before its DMA in issue order, so they never enter the counted waits
-    const int ra = n ? vr0 : Y1;
-    for (int Y = Y0; Y < ra; Y++) put_fill(Y);
-
-    // Progress-based priority (EVAM_PP_PRIO): waves of a SIMD otherwise share issue by age, so the youngest
-    // workgroups' waves lag and end the launch alone; a wave lowers its priority as it passes each quarter of its
-    // rows, so the ones behind get the issue slots when several are ready.
-    ProgressPrio prio(P.prio != 0, n);
-    const int nst = full ? NS * PX : NS;
-    // one output row: row i of the tile's visible rows, ring entry kk (compile-time after unrolling)
-    auto row = [&](int i, int kk, auto has_pad) {
-        constexpr bool PADC = decltype(has_pad)::value;
-        // row i's DMA landed. Issued after it: the DMA of rows i+1 .. i+D-1 (>= NMIN each) and the stores
-        // of rows i-D+1 .. i-1 (nst each)
-        constexpr int SD = D - 1;
-        if (SD == 0) {  // nothing was issued after row i's DMA
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if (i >= SD && i + D - 1 < n) {
-            if (PX == 1 || !full) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NMIN + SD * NS) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 1) * NMIN + SD * NS * PX) : "memory");
-        } else {
-            vmcnt_exact(NMIN * (min(i + D - 1, n - 1) - i) + nst * min(i, SD));
-        }
-#ifdef EVAM_PP_TRACE
-        if (i == 0) EVAM_WSTAMP(3);
-#endif
-        prio.step(i);
-        const int Y = vr0 + i;
-        const uint32_t wb0 = (uint32_t)__builtin_amdgcn_readlane(lb0, i), wb1 = (uint32_t)__builtin_amdgcn_readlane(lb1, i);
-        const int ya = __builtin_amdgcn_readlane(lr0, i), yb = __builtin_amdgcn_readlane(lr1, i);
-        const bool share = ((y0 + ya) >> 1) == ((y0 + yb) >> 1);
-        if (kAblate & 2) {  // diagnostics: no pixel math (no tap reads)
-            put_fill(Y);
-        } else if constexpr (PK) {
-            // BGRx: both taps of a source row are two adjacent dwords; channel c of the pair is one v_perm into
-            // two u16 halves, and the horizontal pass one v_dot2 with the 16x weights
-            const int eo = kk * GRP;
-#pragma unroll
-            for (int j = 0; j < PX; j++) {
-                const uint32_t* ay = reinterpret_cast<const uint32_t*>(aY[j] + eo);
-                const uint32_t qa0 = ay[0], qa1 = ay[1], qb0 = ay[SY / 4], qb1 = ay[SY / 4 + 1];
-                uint32_t v[3];
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const uint32_t sel = 0x0C000C00u | ((uint32_t)(4 + c) << 16) | (uint32_t)c;
-                    const uint32_t ha = __builtin_amdgcn_udot2(
-                        __builtin_bit_cast(evam_u16x2, __builtin_amdgcn_perm(qa1, qa0, sel)),
-                        __builtin_bit_cast(evam_u16x2, wp[j]), 0u, false);
-                    const uint32_t hb = __builtin_amdgcn_udot2(
-                        __builtin_bit_cast(evam_u16x2, __builtin_amdgcn_perm(qb1, qb0, sel)),
-                        __builtin_bit_cast(evam_u16x2, wp[j]), 0u, false);
-                    v[c] = vfinal<OUT>(ha, hb, wb0, wb1);
-                }
-                if constexpr (PADC) {
-                    v[0] = padc[j] ? fill0 : v[0];
-                    v[1] = padc[j] ? fill1 : v[1];
-                    v[2] = padc[j] ? fill2 : v[2];
-                }
-                put(Y, j, v[0], v[1], v[2]);
-            }
-        } else {
-            const int eo = kk * GRP;  // this entry's offset from entry 0
-            // raw taps of the entry into registers: luma bytes of both source rows, chroma of the first
-            // chroma row and, when the second source row has its own, of the second
-            uint32_t rY[PX][4], rC[PX][2][2], rE[PX][2][2];
-            auto raw_c = [&](const uint8_t* a, int o, uint32_t (&c)[2]) {
-                c[0] = a[o];
-                c[1] = FMT == kNV12 ? a[o + 1] : a[o + SV];  // NV12: interleaved UV; I420: the V slot
-            };
-#pragma unroll
-            for (int j = 0; j < PX; j++) {
-                const uint8_t* ay = aY[j] + eo;
-                rY[j][0] = ay[0]; rY[j][1] = ay[1]; rY[j][2] = ay[SY]; rY[j][3] = ay[SY + 1];
-                raw_c(aC0[j], eo, rC[j][0]);
-                raw_c(aC1[j], eo, rC[j][1]);
-            }
-            if (!share) {
-#pragma unroll
-                for (int j = 0; j < PX; j++) {
-                    raw_c(aC0[j], eo + SC, rE[j][0]);
-                    raw_c(aC1[j], eo + SC, rE[j][1]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < PX; j++) {
-                const UVs tA = uvt(rC[j][0][0], rC[j][0][1]), tB = uvt(rC[j][1][0], rC[j][1][1]);
-                const uint32_t yA = luma_term(rY[j][0]), yB = luma_term(rY[j][1]);
-                const uint32_t yC = luma_term(rY[j][2]), yD = luma_term(rY[j][3]);
-                uint32_t h0[3], h1[3];
-                h0[0] = hpass_sat(yA, tA.b, yB, tB.b, wp[j]);
-                h0[1] = hpass_sat(yA, tA.g, yB, tB.g, wp[j]);
-                h0[2] = hpass_sat(yA, tA.r, yB, tB.r, wp[j]);
-                if (share) {  // both vertical taps in one chroma row: its terms serve both source rows
-                    h1[0] = hpass_sat(yC, tA.b, yD, tB.b, wp[j]);
-                    h1[1] = hpass_sat(yC, tA.g, yD, tB.g, wp[j]);
-                    h1[2] = hpass_sat(yC, tA.r, yD, tB.r, wp[j]);
-                    // distinct markers end the two branches, so the compiler does not merge their common
-                    // tail behind register copies of the chroma terms
-                    asm volatile("; strip: shared chroma row" ::"v"(h1[0]), "v"(h1[1]), "v"(h1[2]));
-                } else {
-                    const UVs tC = uvt(rE[j][0][0], rE[j][0][1]), tE = uvt(rE[j][1][0], rE[j][1][1]);
-                    h1[0] = hpass_sat(yC, tC.b, yD, tE.b, wp[j]);
-                    h1[1] = hpass_sat(yC, tC.g, yD, tE.g, wp[j]);
-                    h1[2] = hpass_sat(yC, tC.r, yD, tE.r, wp[j]);
-                    asm volatile("; strip: two chroma rows" ::"v"(h1[0]), "v"(h1[1]), "v"(h1[2]));
-                }
-                uint32_t v[3];
-#pragma unroll
-                for (int c = 0; c < 3; c++) v[c] = vfinal<OUT>(h0[c], h1[c], wb0, wb1);
-                if constexpr (PADC) {
-                    v[0] = padc[j] ? fill0 : v[0];
-                    v[1] = padc[j] ? fill1 : v[1];
-                    v[2] = padc[j] ? fill2 : v[2];
-                }
-                put(Y, j, v[0], v[1], v[2]);
-            }
-        }
-        asm volatile("" ::: "memory");  // issue order is what the counted waits assume
-        if (i + D < n) issue(i + D, kk);  // this entry's reads are done: the stores consumed them
-        asm volatile("" ::: "memory");
-    };
-    auto ring = [&](auto has_pad) {
-        for (int i0 = 0; i0 < n; i0 += D) {
-#pragma unroll
-            for (int kk = 0; kk < D; kk++)
-                if (i0 + kk < n) row(i0 + kk, kk, has_pad);
-        }
-    };
-    if (anypad) ring(std::true_type{});
-    else ring(std::false_type{});
-    // letterbox rows below the ring
-    for (int Y = max(ra, vr1); Y < Y1; Y++) put_fill(Y);
-#ifdef EVAM_PP_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last stores retired
-    EVAM_WSTAMP(4);
-    {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        EVAM_WTRACE_VAL(6, (unsigned long long)xcc);
-    }
-#endif
-}
-
-// Wait until at most n (>= 0, wave-uniform) vector-memory operations of this wave are outstanding, rounded down to
-// 0-4, 6, 8, 12, 16 or 32: waiting for a few more operations than needed is always safe. A binary tree of scalar
-// compares and branches in one asm block: 4-5 compares, one wait and one branch on every path. (The same tree in C was
-// structurised by the compiler into flag registers carried through every level, ~25 scalar instructions per wait;
-// same box, one launch at a time: C1 equal, C1 / I420 +2.2 %, profiles/r06n_vmcnt_asm_ab.txt. The tree itself costs a
-// third of the scalar instructions of an exact 64-case jump, C1 +2 % against it: profiles/r04k2_vmcnt_coarse_ab.txt.)
-__device__ __forceinline__ void vmcnt_le(int n) {
-    n = __builtin_amdgcn_readfirstlane(n);
-    asm volatile(
-        "s_cmp_lt_i32 %0, 8\n\t"
-        "s_cbranch_scc1 5f\n\t"
-        "s_cmp_lt_i32 %0, 16\n\t"
-        "s_cbranch_scc1 2f\n\t"
-        "s_cmp_lt_i32 %0, 32\n\t"
-        "s_cbranch_scc1 1f\n\t"
-        "s_waitcnt vmcnt(32)\n\t"
-        "s_branch 9f\n"
-        "1:\n\t"
-        "s_waitcnt vmcnt(16)\n\t"
-        "s_branch 9f\n"
-        "2:\n\t"
-        "s_cmp_lt_i32 %0, 12\n\t"
-        "s_cbranch_scc1 3f\n\t"
-        "s_waitcnt vmcnt(12)\n\t"
-        "s_branch 9f\n"
-        "3:\n\t"
-        "s_waitcnt vmcnt(8)\n\t"
-        "s_branch 9f\n"
-        "5:\n\t"
-        "s_cmp_lt_i32 %0, 4\n\t"
-        "s_cbranch_scc1 7f\n\t"
-        "s_cmp_lt_i32 %0, 6\n\t"
-        "s_cbranch_scc1 6f\n\t"
-        "s_waitcnt vmcnt(6)\n\t"
-        "s_branch 9f\n"
-        "6:\n\t"
-        "s_waitcnt vmcnt(4)\n\t"
-        "s_branch 9f\n"
-        "7:\n\t"
-        "s_cmp_lt_i32 %0, 2\n\t"
-        "s_cbranch_scc1 8f\n\t"
-        "s_cmp_lt_i32 %0, 3\n\t"
-        "s_cbranch_scc1 4f\n\t"
-        "s_waitcnt vmcnt(3)\n\t"
-        "s_branch 9f\n"
-        "4:\n\t"
-        "s_waitcnt vmcnt(2)\n\t"
-        "s_branch 9f\n"
-        "8:\n\t"
-        "s_cmp_lt_i32 %0, 1\n\t"
-        "s_cbranch_scc1 10f\n\t"
-        "s_waitcnt vmcnt(1)\n\t"
-        "s_branch 9f\n"
-        "10:\n\t"
-        "s_waitcnt vmcnt(0)\n"
-        "9:"
-        ::"s"(n)
-        : "scc", "memory");
-}
-
-// Band kernel for uniform 4:2:0 batches whose consecutive output rows share source rows (vertical
-// upscales: C1). One wave owns one band of TH output rows of one 64·PX-column strip (lane l: the PX
-// adjacent columns X0 + PX l ..), with no workgroup barrier after the prologue:
-//  * every source row the band reads (luma rows r0(first) .. r1(last), and their chroma rows) is staged
-//    once, in need order, by one LDS-DMA instruction per row segment at the start; output row i then
-//    waits with one counted vmcnt for the rows it needs, so its arithmetic overlaps the later rows' DMA;
-//  * horizontal results stay in registers per source row (HA: row pa, HB: row pb) and the BT.601 chroma
-//    terms per chroma row, so a source row is converted and filtered once however many output rows read
-//    it (~0.84 source rows per output row at 432 -> 512);
-//  * coefficients of the strip's columns (per lane) and of the band's rows (one per lane, v_readlane)
-//    come from the kernels' shared linear_coef: no table loads (the host's column table loaded at entry instead
-//    was 1.5 % slower on C1: the per-pixel setup then waits for the load, profiles/r05t_c1_band_table_dd_ab.txt);
-//  * DD (six-column lanes, band_six_columns): a lane's 4 pixels read 6 source columns and 3 chroma columns, so a
-//    source row costs 6 luma and 18 saturating sums instead of 8 and 24, a chroma row 3 conversions instead of 8;
-//  * each channel of a row leaves as one PX-wide store per lane.
-// Workgroups of up to four waves: the strips of one band of one item.
-// NHWC (interleaved u8 output, PX = 4): a lane's four pixels are 12 adjacent bytes of the slot, packed from the
-// same sums into three dwords and stored as one 12-byte store per row (the host admits it where that store is
-// dword-aligned: DW % 4 == 0 and a 4-byte-aligned tensor base).
-template <int FMT, int OUT, int PX, int DD, bool NHWC = false>
-__global__ __launch_bounds__(256) void evam_pp_band(const TParams P) {
-    static_assert(!NHWC || (OUT == 0 && PX == 4), "the interleaved band store is u8 at four pixels per lane");
-    constexpr int NS = NHWC ? 1 : 3;  // stores per output row
-    __shared__ __attribute__((aligned(16))) float lut_s[OUT == 1 ? 768 : 4];
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    if (kAblate & 128) return;  // diagnostics: launch cost only
-    static_assert(FMT == kNV12 || FMT == kI420, "4:2:0 sources");
-    static_assert(PX == 1 || PX == 2 || PX == 4, "pixels per lane");
-    static_assert(!DD || PX == 4, "six-column lanes hold 4 pixels");
-    constexpr int NPC = FMT == kI420 ? 2 : 1;  // chroma planes
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    EVAM_WSTAMP(0);
-    // grid (strip group, band, item): every kernel-argument load of the prologue has an address known at entry,
-    // so they all go out in one batch (one round trip before the first DMA)
-    const int item = blockIdx.z, band = blockIdx.y;
-    const ItemArg& it = P.items[item];
-    const ColSpan sf = P.sfoot[min((int)blockIdx.x * 8 + wave, kSfoot - 1)];
-    const int p_nw = P.nw, p_TH = P.TH, p_DH = P.DH, p_DW = P.DW;
-    int p_ns = P.nstrips, k_wb = P.wave_bytes;
-    const uint8_t* p0 = it.plane[0];
-    const uint8_t* p1 = it.plane[1];
-    const uint8_t* p2 = it.plane[2];
-    const int pitch0 = it.pitch[0], pitch1 = it.pitch[1], pitch2 = it.pitch[2];
-    const int x0 = it.x0, y0 = it.y0;
-    // The row table's and the LUT DMA's parameters join the batch as opaque values the compiler cannot reload
-    // (loaded where first used, they were two more dependent kernel-argument round trips before the first DMA);
-    // one statement, so every load goes out before the one wait (30 operands at most: the output's
-    // parameters, first needed at the first store, are left out).
-    double k_scale_y = P.scale_y;
-    int k_ch = P.ch, k_rgb = P.color_rgb;
-    const float* k_lut = P.lut;
-    asm volatile("" : "+s"(k_scale_y), "+s"(k_ch), "+s"(k_lut), "+s"(k_rgb), "+s"(p_ns), "+s"(k_wb)
-                 : "s"(p_nw), "s"(p_TH), "s"(p_DH), "s"(p_DW), "s"(P.ox), "s"(P.rw), "s"(P.oy), "s"(P.rh),
-                   "s"(P.segY), "s"(P.segC), "s"(P.nrY), "s"(p0), "s"(p1), "s"(p2), "s"(pitch0),
-                   "s"(pitch1), "s"(pitch2), "s"(x0), "s"(y0), "s"(it.index), "s"(sf.x), "s"(sf.y));
-    const int strip = (int)blockIdx.x * p_nw + wave;
-    const bool live = strip < p_ns;
-    const int Y0 = band * p_TH, Y1 = min(Y0 + p_TH, p_DH);
-    const int X0 = strip * 64 * PX;
-    const bool cols = live && sf.x >= 0;
-    int fsY = 0, nY = 0, fsC = 0, nC = 0;
-    if (cols) footprint_chunks(FMT, 1, x0 + sf.x, x0 + sf.y, fsY, nY, fsC, nC);
-    const int vr0 = max(Y0, P.oy), vr1 = min(Y1, P.oy + P.rh);
-    const int n = cols && vr1 > vr0 ? vr1 - vr0 : 0;  // visible rows of the band (<= 64)
-
-    // row table, one visible row per lane: source rows relative to the crop, weights << 8
-    int lr0 = 0, lr1 = 0, lb0 = 0, lb1 = 0;
-    if (lane < n) {
-        int sy, b0, b1;
-        linear_coef(vr0 + lane - P.oy, k_scale_y, k_ch, false, sy, b0, b1);
-        lr0 = min(max(sy, 0), k_ch - 1);
-        lr1 = min(max(sy + 1, 0), k_ch - 1);
-        lb0 = b0 << 8;
-        lb1 = b1 << 8;
-    }
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p0, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc((void*)p1, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)(NPC == 2 ? p2 : p1), (short)0, 0x7FFFFFFF, 0x00020000);
-    uint8_t* const wbuf = smem + wave * k_wb;
-    const int segY = P.segY, segC = P.segC;
-    uint8_t* const cbuf = wbuf + P.nrY * segY;  // chroma rows; I420: V row k at + segC / 2 (segC holds U | V)
-    // source rows of the band (rows are monotonic in the output row): luma [rlo, rhi], chroma [clo, chi]
-    const int rlo = n ? __builtin_amdgcn_readlane(lr0, 0) : 0;
-    const int rhi = n ? __builtin_amdgcn_readlane(lr1, n - 1) : -1;
-    const int clo = (y0 + rlo) >> 1;
-    // The wave counts every vector-memory operation it issues (pos) and remembers pos right after each luma row's
-    // DMA (lane r - rlo of dpos), so every wait below is exact.
-    int pos = 0, dpos = 0;
-    // fp32: the LUT (3 KB, sections in source channel order) by LDS-DMA ahead of the rows, so no VGPR waits
-    // on it and the rows' counted waits are unaffected (it is older)
-    if constexpr (OUT == 1) {
-        for (int c0 = wave * 64; c0 < 192; c0 += (int)(blockDim.x >> 6) * 64, pos++) {
-            const int c = c0 + lane, sec = c >> 6;
-            const int src = ((k_rgb ? 2 - sec : sec) * 64 + (c & 63)) * 16;
-            const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void*)k_lut, (short)0, 3072, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsL, (__attribute__((address_space(3))) void*)((uint8_t*)lut_s + c0 * 16),
-                                                     16, (uint32_t)src, 0, 0, 0);
-        }
-    }
-    const int lut_pos = pos;
-    // DMA in need order: luma row r, then its chroma row when r is the first row reading it. Rows go out up to
-    // `ahead` source rows past the last row the current output row reads (EVAM_PP_BAND_AHEAD; 64: the whole band
-    // at once), so a wave's first rows do not queue behind the rest of the band in the launch's opening burst.
-    int rnext = rlo, cprev = -1;
-    const int ahead = P.ahead;
-    auto issue_to = [&](int rmax) {
-        const uint32_t vo = (uint32_t)lane * 16u;
-        for (; rnext <= rmax; rnext++) {
-            const int r = rnext, ya = y0 + r, c = ya >> 1;
-            if (lane < nY)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsY, (__attribute__((address_space(3))) void*)(wbuf + (r - rlo) * segY),
-                                                         16, vo, ya * pitch0 + fsY, EVAM_PP_LOAD_AUX, 0);
-            pos++;
-            if (c != cprev) {
-                uint8_t* cb = cbuf + (c - clo) * segC;
-                if (lane < nC) {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsU, (__attribute__((address_space(3))) void*)cb, 16, vo,
-                                                             c * pitch1 + fsC, EVAM_PP_LOAD_AUX, 0);
-                    if constexpr (NPC == 2)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (__attribute__((address_space(3))) void*)(cb + segC / 2),
-                                                                 16, vo, c * pitch2 + fsC, EVAM_PP_LOAD_AUX, 0);
-                }
-                pos += NPC;
-                cprev = c;
-            }
-            dpos = lane == r - rlo ? pos : dpos;
-        }
-    };
-    if (n) issue_to(min(rhi, __builtin_amdgcn_readlane(lr1, 0) + ahead));
-    EVAM_WSTAMP(1);
-    EVAM_WTRACE_VAL(5, (unsigned long long)n << 48);
-
-    if constexpr (OUT == 1) {
-        vmcnt_le(pos - lut_pos);  // this wave's LUT pieces landed (issued before every row)
-        lds_barrier();            // ... and every other wave's (LDS only: the rows' DMA stays in flight)
-    }
-    if (!live) return;
-
-    // per-lane column state: tap offsets in the staged rows (tap 0 low, tap 1 high half), packed 11-bit
-    // weights, padding columns
-    const int X = X0 + lane * PX;
-    const bool xin = X < p_DW;  // DW % PX == 0: a lane's pixels are all in or all out
-    uint32_t lY[PX], lC[PX], wp[PX];
-    bool padc[PX];
-    bool anyp = false;
-#pragma unroll
-    for (int j = 0; j < PX; j++) {
-        lY[j] = lC[j] = wp[j] = 0;
-        padc[j] = true;
-        const int dx = X + j - P.ox;
-        if (cols && xin && dx >= 0 && dx < P.rw) {
-            int s0, a0, a1;
-            linear_coef(dx, P.scale_x, P.cw, true, s0, a0, a1);
-            const int ca = x0 + s0, cb = x0 + min(s0 + 1, P.cw - 1);
-            lY[j] = (uint32_t)(ca - fsY) | ((uint32_t)(cb - fsY) << 16);
-            if constexpr (FMT == kNV12)
-                lC[j] = (uint32_t)(2 * (ca >> 1) - fsC) | ((uint32_t)(2 * (cb >> 1) - fsC) << 16);
-            else
-                lC[j] = (uint32_t)((ca >> 1) - fsC) | ((uint32_t)((cb >> 1) - fsC) << 16);
-            wp[j] = (uint32_t)a0 | ((uint32_t)a1 << 16);
-            padc[j] = false;
-        }
-        anyp |= xin && padc[j];
-    }
-    const bool anypad = __builtin_amdgcn_ballot_w64(anyp) != 0;
-    if (kAblate & 64) {  // diagnostics: prologue only (row / column coefficients, the first rows' DMA landed)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("" ::"v"(lY[0]), "v"(lC[0]), "v"(wp[0]), "v"(lb0), "v"(lb1), "v"((int)anypad));
-        return;
-    }
-    const size_t esz = OUT == 1 ? 4 : 1;
-    const uint32_t vo = (uint32_t)(xin ? X : 0) * (uint32_t)(NHWC ? 3 * esz : esz);
-    const size_t plane = (size_t)p_DW * p_DH;
-    uint8_t* const d0 = reinterpret_cast<uint8_t*>(P.dst) + (size_t)(P.slot_offset + it.index * P.slot_stride) * 3 * plane * esz;
-    uint8_t* const d1 = d0 + plane * esz;
-    uint8_t* const d2 = d1 + plane * esz;
-    // (NHWC: rsO0 is the whole slot)
-    const __amdgpu_buffer_rsrc_t rsO0 = __builtin_amdgcn_make_buffer_rsrc((void*)(!NHWC && k_rgb ? d2 : d0), (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsO1 = __builtin_amdgcn_make_buffer_rsrc((void*)d1, (short)0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsO2 = __builtin_amdgcn_make_buffer_rsrc((void*)(k_rgb ? d0 : d2), (short)0, 0x7FFFFFFF, 0x00020000);
-    const uint32_t fq0 = P.fill & 0xFF, fq1 = (P.fill >> 8) & 0xFF, fq2 = (P.fill >> 16) & 0xFF;
-    const uint32_t fsh = OUT == 1 ? 2 : 0;
-    const uint32_t fill0 = (k_rgb ? fq2 : fq0) << fsh, fill1 = fq1 << fsh, fill2 = (k_rgb ? fq0 : fq2) << fsh;
-    const uint8_t* lutb = reinterpret_cast<const uint8_t*>(lut_s);
-    // one row of the strip: v[c][j] = LUT byte offsets (fp32) or bytes (u8) in source channel order; the
-    // row offset in the VGPR offset (soffset 0: the store-data hazard of wide stores, see evam_pp_wave)
-    // NHWC: the lane's 12 bytes of row Y from the sums x (byte = x >> 2), source channel order in, output order out
-    auto put_nhwc = [&](int Y, const uint32_t (&x)[3][PX]) {
-        if constexpr (NHWC) {
-            if (!xin) return;
-            uint32_t a[4], c[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                a[j] = k_rgb ? x[2][j] : x[0][j];
-                c[j] = k_rgb ? x[0][j] : x[2][j];
-            }
-            const evam_v3i q = {(int)pack4_u8_sums(a[0], x[1][0], c[0], a[1]), (int)pack4_u8_sums(x[1][1], c[1], a[2], x[1][2]),
-                                (int)pack4_u8_sums(c[2], a[3], x[1][3], c[3])};
-            __builtin_amdgcn_raw_buffer_store_b96(q, rsO0, vo + (uint32_t)(Y * p_DW) * 3u, 0, EVAM_PP_STORE_AUX);
-        }
-    };
-    auto put = [&](int Y, const uint32_t (&v)[3][PX]) {
-        if (!xin) return;
-        if constexpr (NHWC) {
-            uint32_t x[3][PX];
-#pragma unroll
-            for (int j = 0; j < PX; j++)
-#pragma unroll
-                for (int c = 0; c < 3; c++) x[c][j] = v[c][j] << 2;
-            put_nhwc(Y, x);
-            return;
-        }
-        const uint32_t off = vo + (uint32_t)(Y * p_DW) * (uint32_t)esz;
-        store_off<OUT, PX>(rsO0, off, lutb, v[0]);
-        store_off<OUT, PX>(rsO1, off, lutb + 1024, v[1]);
-        store_off<OUT, PX>(rsO2, off, lutb + 2048, v[2]);
-    };
-    auto put_fill = [&](int Y) {
-        uint32_t v[3][PX];
-#pragma unroll
-        for (int j = 0; j < PX; j++) { v[0][j] = fill0; v[1][j] = fill1; v[2][j] = fill2; }
-        put(Y, v);
-    };
-    for (int Y = Y0; Y < (n ? vr0 : Y1); Y++) {  // letterbox rows above
-        put_fill(Y);
-        pos += NS;
-    }
-
-    uint32_t kb = kKBs, kg = kKGs, kr = kKRs;
-    int cvg = kCVG, cug = kCUG;
-    asm volatile("" : "+v"(kb), "+v"(kg), "+v"(kr), "+s"(cvg), "+s"(cug));
-    auto uvt = [&](uint32_t U, uint32_t V) {
-        int gu = __mul24((int)U, cug) + (int)kg;
-        asm("" : "+v"(gu));
-        return UVs{__umul24(U, (uint32_t)kCUB) + kb, (uint32_t)(__mul24((int)V, cvg) + gu), __umul24(V, (uint32_t)kCVR) + kr};
-    };
-    // chroma terms of the chroma row cc for both taps of every pixel (kept across source rows)
-    UVs tA[PX], tB[PX];
-    int cc = -1;
-    auto chroma_row = [&](int c) {
-        const uint8_t* cb = cbuf + (c - clo) * segC;
-        cc = c;
-        if constexpr (DD) {  // the chroma columns of (c0, c1), (c2, c3), (c4, c5) in tA[0..2]
-            const uint32_t o[3] = {lC[0] & 0xFFFF, lC[1] >> 16, lC[2] >> 16};
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const uint8_t* a = cb + o[k];
-                tA[k] = uvt(a[0], FMT == kNV12 ? a[1] : a[segC / 2]);
-            }
-            return;
-        }
-#pragma unroll
-        for (int j = 0; j < PX; j++) {
-            const uint8_t* a0 = cb + (lC[j] & 0xFFFF);
-            const uint8_t* a1 = cb + (lC[j] >> 16);
-            if constexpr (FMT == kNV12) {
-                tA[j] = uvt(a0[0], a0[1]);
-                tB[j] = uvt(a1[0], a1[1]);
-            } else {
-                tA[j] = uvt(a0[0], a0[segC / 2]);
-                tB[j] = uvt(a1[0], a1[segC / 2]);
-            }
-        }
-    };
-    // A source row's 3 PX filtered values travel as 64-bit register pairs (value k of pixel j at flat index
-    // 3 j + k), so the HA <- HB copy of a one-row step is one v_pk_mov_b32 per two values.
-    constexpr int NH = (3 * PX + 1) / 2;
-    struct HRow { uint64_t p[NH]; };
-    auto hget = [](const HRow& h, int j, int k) -> uint32_t {
-        const int f = 3 * j + k;
-        return (uint32_t)(h.p[f >> 1] >> (32 * (f & 1)));
-    };
-    auto hpack = [](HRow& h, const uint32_t (&H)[PX][3]) {
-#pragma unroll
-        for (int i = 0; i < NH; i++) {
-            const int f0 = 2 * i, f1 = 2 * i + 1;
-            const uint32_t lo = H[f0 / 3][f0 % 3], hi = f1 < 3 * PX ? H[f1 / 3][f1 % 3] : 0u;
-            h.p[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-        }
-    };
-    // horizontal pass of source row r (crop-relative) into HR
-    auto hrow = [&](int r, HRow& HR) {
-        uint32_t H[PX][3];
-        const int c = (y0 + r) >> 1;
-        if (c != cc) chroma_row(c);
-        const uint8_t* yb = wbuf + (r - rlo) * segY;
-        if constexpr (DD) {  // columns c0..c5: pixel 0 (c0, c1), 1 (c1, c2), 2 (c3, c4), 3 (c4, c5)
-            const uint32_t yl[6] = {luma_term(yb[lY[0] & 0xFFFF]), luma_term(yb[lY[0] >> 16]), luma_term(yb[lY[1] >> 16]),
-                                    luma_term(yb[lY[2] & 0xFFFF]), luma_term(yb[lY[2] >> 16]), luma_term(yb[lY[3] >> 16])};
-#pragma unroll
-            for (int ch3 = 0; ch3 < 3; ch3++) {
-                uint32_t sm[6];
-#pragma unroll
-                for (int k = 0; k < 6; k++) {
-                    const UVs& t = tA[k >> 1];
-                    sm[k] = __builtin_elementwise_add_sat(yl[k], ch3 == 0 ? t.b : (ch3 == 1 ? t.g : t.r));
-                }
-                H[0][ch3] = hpass_sums(sm[0], sm[1], wp[0]) & kVMask;
-                H[1][ch3] = hpass_sums(sm[1], sm[2], wp[1]) & kVMask;
-                H[2][ch3] = hpass_sums(sm[3], sm[4], wp[2]) & kVMask;
-                H[3][ch3] = hpass_sums(sm[4], sm[5], wp[3]) & kVMask;
-            }
-            hpack(HR, H);
-            return;
-        }
-#pragma unroll
-        for (int j = 0; j < PX; j++) {
-            const uint32_t yA = luma_term(yb[lY[j] & 0xFFFF]), yB = luma_term(yb[lY[j] >> 16]);
-            // masked once per source row here rather than per output row in vfinal (each row serves ~2.4 output rows)
-            H[j][0] = hpass_sat(yA, tA[j].b, yB, tB[j].b, wp[j]) & kVMask;
-            H[j][1] = hpass_sat(yA, tA[j].g, yB, tB[j].g, wp[j]) & kVMask;
-            H[j][2] = hpass_sat(yA, tA[j].r, yB, tB[j].r, wp[j]) & kVMask;
-        }
-        hpack(HR, H);
-    };
-    HRow HA, HB;
-    int pa = -1, pb = -1;
-    const int nst = NS;  // stores per output row (one PX-wide store per channel; NHWC: one for all three)
-    // progress-based priority (EVAM_PP_PRIO), as in the strip kernel
-    ProgressPrio prio(P.prio != 0, n);
-    for (int i = 0; i < n; i++) {
-        prio.step(i);
-        const int ra = __builtin_amdgcn_readlane(lr0, i), rb = __builtin_amdgcn_readlane(lr1, i);
-        issue_to(rb);  // (issued already unless `ahead` is 0)
-        vmcnt_le(pos - __builtin_amdgcn_readlane(dpos, rb - rlo));  // rows up to rb landed
-#ifdef EVAM_PP_TRACE
-        if (i == 0) {
-            EVAM_WSTAMP(2);
-            EVAM_WSTAMP(3);
-        }
-#endif
-        const uint32_t wb0 = (uint32_t)__builtin_amdgcn_readlane(lb0, i), wb1 = (uint32_t)__builtin_amdgcn_readlane(lb1, i);
-        if (kAblate & 2) {  // diagnostics: no pixel math (no tap reads), stores and DMA kept
-            put_fill(vr0 + i);
-            pos += nst;
-            asm volatile("" ::: "memory");
-            if (i + 1 < n) issue_to(min(rhi, __builtin_amdgcn_readlane(lr1, i + 1) + ahead));
-            asm volatile("" ::: "memory");
-            continue;
-        }
-        // HA <- row ra, HB <- row rb, reusing what the previous output row filtered (wave-uniform branches)
-        if (ra != pa) {
-            if (ra == pb) {
-                HA = HB;
-            } else {
-                hrow(ra, HA);
-            }
-        }
-        if (rb == ra) {
-            HB = HA;
-        } else if (rb != pb || ra == pb) {  // HB was overwritten into HA above, or holds another row
-            hrow(rb, HB);
-        }
-        pa = ra;
-        pb = rb;
-        uint32_t v[3][PX];
-#pragma unroll
-        for (int j = 0; j < PX; j++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) v[c][j] = vfinal_masked<OUT>(hget(HA, j, c), hget(HB, j, c), wb0, wb1);
-        if constexpr (OUT == 0 && PX == 4) {  // u8, 4 pixels per lane: the sums packed by pack4_u8_sums
-            uint32_t x[3][4];
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-#pragma unroll
-                for (int c = 0; c < 3; c++) x[c][j] = mulhi_u24(wb0, hget(HA, j, c)) + mulhi_u24(wb1, hget(HB, j, c)) + 2u;
-            if (anypad) {  // padding columns: the fill byte as a sum (x >> 2 == fill)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    x[0][j] = padc[j] ? fill0 << 2 : x[0][j];
-                    x[1][j] = padc[j] ? fill1 << 2 : x[1][j];
-                    x[2][j] = padc[j] ? fill2 << 2 : x[2][j];
-                }
-            }
-            if constexpr (NHWC) {
-                put_nhwc(vr0 + i, x);
-            } else if (xin) {
-                const uint32_t off = vo + (uint32_t)((vr0 + i) * p_DW);
-                __builtin_amdgcn_raw_buffer_store_b32(pack4_u8_sums(x[0][0], x[0][1], x[0][2], x[0][3]), rsO0, off, 0,
-                                                      EVAM_PP_STORE_AUX);
-                __builtin_amdgcn_raw_buffer_store_b32(pack4_u8_sums(x[1][0], x[1][1], x[1][2], x[1][3]), rsO1, off, 0,
-                                                      EVAM_PP_STORE_AUX);
-                __builtin_amdgcn_raw_buffer_store_b32(pack4_u8_sums(x[2][0], x[2][1], x[2][2], x[2][3]), rsO2, off, 0,
-                                                      EVAM_PP_STORE_AUX);
-            }
-            pos += nst;
-            asm volatile("" ::: "memory");  // issue order is what the counted waits assume
-            if (i + 1 < n) issue_to(min(rhi, __builtin_amdgcn_readlane(lr1, i + 1) + ahead));
-            asm volatile("" ::: "memory");
-            continue;
-        }
-        if (anypad) {
-#pragma unroll
-            for (int j = 0; j < PX; j++) {
-                v[0][j] = padc[j] ? fill0 : v[0][j];
-                v[1][j] = padc[j] ? fill1 : v[1][j];
-                v[2][j] = padc[j] ? fill2 : v[2][j];
-            }
-        }
-        put(vr0 + i, v);
-        pos += nst;
-        asm volatile("" ::: "memory");  // issue order is what the counted waits assume
-        if (i + 1 < n) issue_to(min(rhi, __builtin_amdgcn_readlane(lr1, i + 1) + ahead));
-        asm volatile("" ::: "memory");
-    }
-    for (int Y = max(n ? vr1 : Y1, Y0); Y < Y1; Y++) put_fill(Y);  // letterbox rows below
-#ifdef EVAM_PP_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    EVAM_WSTAMP(4);
-    {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        EVAM_WTRACE_VAL(6, (unsigned long long)xcc);
-    }
-#endif
-}
-
+namespace {
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt_stores(int nk) {
@@ -2890,149 +1657,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_num_sgpr(96))) void
     EVAM_STAMP(3);
 }
 
-// ------------------------------------------------------------------------------------------------
-// device-resident ROI lists (evam_pp_ssd_rois, evam_pp_run_device_rois)
-// ------------------------------------------------------------------------------------------------
-// Records kernel: one thread per (list entry, row tile) of the list's capacity writes that unit's RoiRec, in list
-// order, from the entry and the per-source table (RecFrame per source: the frame half of a record). An entry past
-// min(*count, cap), with a src_index outside the sources, or whose rect clips to nothing (roi_clip, the host's own
-// rule) gets the row range [0, 0): evam_pp_roi<.., DEV = true> returns on it. Ordinary vector stores: the ROI kernel
-// launched next on the stream sees them through the kernel boundary.
-struct DParams {
-    const evam_roi* rois;
-    const uint32_t* count;
-    const uint4* srcs;  // [n_srcs][3]
-    RoiRec* recs;       // [cap * tiles]
-    int32_t* status;    // NULL or [cap]
-    int cap, n_srcs, tiles, TH, DH, fmt;
-};
+}  // namespace
 
-__global__ __launch_bounds__(kThreads) void evam_pp_roi_records(const DParams P) {
-    const int u = blockIdx.x * kThreads + threadIdx.x;
-    if (u >= P.cap * P.tiles) return;
-    const int e = u / P.tiles, t = u - e * P.tiles;
-    const uint32_t cnt = *P.count;
-    bool live = (uint32_t)e < cnt;  // e < cap by the grid
-    int st = 0;
-    uint4 l0 = {0u, 0u, 0u, 0u}, l1 = l0, l2 = l0;
-    int rx = 0, ry = 0, rw = 0, rh = 0;
-    if (live) {
-        const int32_t* r = reinterpret_cast<const int32_t*>(P.rois + e);
-        const int si = r[0];
-        rx = r[1]; ry = r[2]; rw = r[3]; rh = r[4];
-        if ((unsigned)si >= (unsigned)P.n_srcs) {
-            st = EVAM_PP_ERR_INVALID_ARG;
-            live = false;
-        } else {
-            l0 = P.srcs[3 * si];
-            l1 = P.srcs[3 * si + 1];
-            l2 = P.srcs[3 * si + 2];  // pitch[2], width | height << 16, 0, 0
-            Geom g;
-            if (roi_clip(P.fmt, (int)(l2.y & 0xFFFF), (int)(l2.y >> 16), true, rx, ry, rw, rh, g)) {
-                st = EVAM_PP_ERR_EMPTY_ROI;
-                live = false;
-            }
-        }
-    }
-    const uint32_t row0 = live ? (uint32_t)(t * P.TH) : 0u;
-    const uint32_t row1 = live ? (uint32_t)min(P.DH, (t + 1) * P.TH) : 0u;
-    uint4* o = reinterpret_cast<uint4*>(P.recs + u);
-    o[0] = l0;
-    o[1] = l1;
-    o[2] = make_uint4(l2.x, l2.y, (uint32_t)rx, (uint32_t)ry);
-    o[3] = make_uint4((uint32_t)rw, (uint32_t)rh, (uint32_t)e, row0 | (row1 << 16));
-    if (t == 0 && P.status) P.status[e] = st;
-}
+#include "evam_rois_kernels.h"
 
-// SSD rows -> ROI list, an ordered compaction in three launches: evam_pp_ssd_rows<false> counts the accepted rows
-// of every item (one workgroup per item), evam_pp_ssd_scan turns the counts into each item's first list position and
-// the total, evam_pp_ssd_rows<true> evaluates the rows again and writes every accepted rect at its position: item
-// order, then row order, as the host path lists them. ssd_row_rect (evam_geom.h) is the host's arithmetic.
-struct SsdParams {
-    const float* det;          // [n_items][k][7]
-    const int2* sizes;         // per item: its frame's (width, height)
-    const evam_transform* xf;  // per item, or NULL: identity
-    const int32_t* labels;     // accepted label ids, or NULL: all
-    uint32_t* item_count;      // [n_items]
-    uint32_t* item_off;        // [n_items]
-    evam_roi* rois;
-    uint32_t* count;
-    int n_items, k, n_labels, TW, TH, cap;
-    float threshold;
-    int32_t* out_labels;       // evam_pp_ssd_rois_ex (LAB): the label of each list entry, [cap]
-};
-
-template <bool EMIT, bool LAB = false>
-__global__ __launch_bounds__(kThreads) void evam_pp_ssd_rows(const SsdParams P) {
-    __shared__ int s_end;
-    __shared__ uint32_t s_w[kThreads / 64];
-    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* d = P.det + (size_t)i * (size_t)P.k * 7;
-    if (tid == 0) s_end = P.k;
-    __syncthreads();
-    // the rows before the first image_id < 0
-    for (int r = tid; r < P.k; r += kThreads)
-        if (d[(size_t)r * 7] < 0.f) {
-            atomicMin(&s_end, r);
-            break;
-        }
-    __syncthreads();
-    const int kend = s_end;
-    const int2 wh = P.sizes[i];
-    const evam_transform* xf = P.xf ? P.xf + i : nullptr;
-    const uint32_t base = EMIT ? P.item_off[i] : 0u;
-    uint32_t total = 0;
-    for (int r0 = 0; r0 < kend; r0 += kThreads) {  // kend is uniform: every thread takes every barrier
-        const int r = r0 + tid;
-        int x = 0, y = 0, w = 0, h = 0;
-        const bool acc = r < kend && ssd_row_rect(d + (size_t)r * 7, xf, wh.x, wh.y, P.TW, P.TH, P.threshold, P.labels,
-                                                  P.n_labels, x, y, w, h);
-        const unsigned long long m = __ballot(acc);
-        if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (int v = 0; v < kThreads / 64; v++) {
-            before += v < wave ? s_w[v] : 0u;
-            all += s_w[v];
-        }
-        if (EMIT && acc) {
-            const uint32_t pos = base + total + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (pos < (uint32_t)P.cap) {
-                int32_t* o = reinterpret_cast<int32_t*>(P.rois + pos);
-                o[0] = i; o[1] = x; o[2] = y; o[3] = w; o[4] = h;
-                if (LAB) {  // int(label), as the host path truncates it
-                    const float lf = d[(size_t)r * 7 + 1];
-                    P.out_labels[pos] = (lf - lf == 0.f) && lf < 2147483648.f && lf >= -2147483648.f ? (int32_t)lf : 0;
-                }
-            }
-        }
-        total += all;
-        __syncthreads();  // s_w is rewritten by the next chunk
-    }
-    if (!EMIT && tid == 0) P.item_count[i] = total;
-}
-
-__global__ __launch_bounds__(kThreads) void evam_pp_ssd_scan(const uint32_t* cnt, uint32_t* off, int n, uint32_t* total) {
-    __shared__ uint32_t s[kThreads];
-    const int tid = threadIdx.x;
-    uint32_t running = 0;
-    for (int i0 = 0; i0 < n; i0 += kThreads) {
-        const int i = i0 + tid;
-        const uint32_t v = i < n ? cnt[i] : 0u;
-        s[tid] = v;
-        __syncthreads();
-        for (int d = 1; d < kThreads; d <<= 1) {  // inclusive scan of the chunk
-            const uint32_t a = tid >= d ? s[tid - d] : 0u;
-            __syncthreads();
-            s[tid] += a;
-            __syncthreads();
-        }
-        if (i < n) off[i] = running + s[tid] - v;
-        running += s[kThreads - 1];
-        __syncthreads();
-    }
-    if (tid == 0) *total = running;
-}
+namespace {
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -3417,6 +2046,21 @@ static long g_hp_n;
 #define HP(i) (void)0
 #endif
 
+namespace {
+
+struct RecFrame { __m128i l[3]; };  // a record's bytes 0-47 for one source (bytes 40-47 zero)
+RecFrame rec_frame(const evam_image& s) {
+    RoiRec r;
+    memset(&r, 0, sizeof(r));
+    for (int p = 0; p < 3; p++) { r.plane[p] = s.planes[p]; r.pitch[p] = s.pitch[p]; }
+    r.width = (uint16_t)s.width; r.height = (uint16_t)s.height;
+    RecFrame f;
+    memcpy(&f, &r, sizeof(f));
+    return f;
+}
+
+}  // namespace
+
 struct evam_pp {
     int device = 0;
     int n_cu = 256;
@@ -3712,6 +2356,47 @@ void block_lut(evam_pp* h, const evam_preproc* cfg, uint8_t* blk) {
     memcpy(blk, h->lut, kLutBytes);
 }
 
+// The checks of dst and cfg that evam_pp_run(_slots) and evam_pp_run_device_rois share, in the order both report them.
+int check_output(const char* who, const evam_preproc* cfg, const evam_tensor* dst) {
+    if (!dst->data) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst->data is NULL", who);
+    if (dst->c != 3) return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: dst must have 3 channels (got %d)", who, dst->c);
+    if (dst->n <= 0 || dst->h <= 0 || dst->w <= 0)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad dst shape %dx%dx%dx%d", who, dst->n, dst->c, dst->h, dst->w);
+    if (cfg->out_dtype != EVAM_DTYPE_U8 && cfg->out_dtype != EVAM_DTYPE_F32 && cfg->out_dtype != EVAM_DTYPE_F16 &&
+        cfg->out_dtype != EVAM_DTYPE_BF16)
+        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: unknown out_dtype %d", who, cfg->out_dtype);
+    if (cfg->resize_mode < 0 || cfg->resize_mode > 2)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: unknown resize_mode %d", who, cfg->resize_mode);
+    if ((cfg->norm_flags & EVAM_NORM_MEAN_STD) && cfg->out_dtype != EVAM_DTYPE_U8)
+        for (int c = 0; c < 3; c++)
+            if (cfg->std[c] == 0.f) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: std[%d] == 0", who, c);
+    const int64_t plane = (int64_t)dst->w * dst->h;
+    if (plane * 3 * (int64_t)dst->n > ((int64_t)1 << 40)) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst too large", who);
+    // The kernels address one output plane with 32-bit byte offsets.
+    if (plane * out_esz(out_kind(cfg->out_dtype)) > INT32_MAX)
+        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst plane %dx%d exceeds 2 GiB", who, dst->w, dst->h);
+    return 0;
+}
+
+uint32_t pack_fill(const evam_preproc* cfg) {
+    return (uint32_t)cfg->fill[0] | ((uint32_t)cfg->fill[1] << 8) | ((uint32_t)cfg->fill[2] << 16);
+}
+
+// The launch fields of the ROI kernel's arguments (the planner has set the rest), for records at `recs`.
+void roi_launch_fields(QParams& q, const RoiRec* recs, const float* lut, const evam_preproc* cfg, const evam_tensor* dst,
+                       int slot_offset, int slot_stride, int prio) {
+    q.recs = recs;
+    q.lut = lut;
+    q.dst = dst->data;
+    q.mode = cfg->resize_mode;
+    q.placement = cfg->placement;
+    q.slot_offset = slot_offset;
+    q.slot_stride = slot_stride;
+    q.color_rgb = cfg->color_order == EVAM_COLOR_RGB;
+    q.fill = pack_fill(cfg);
+    q.prio = prio;
+}
+
 // evam_pp_run and evam_pp_run_slots. slots == NULL: item i -> slot dst->slot_offset + i * dst->slot_stride; else item i
 // -> slot slots[i]. The kernels read one output index per item (ItemArg / ItemDesc .index, RoiRec .item) and compute
 // slot = slot_offset + index * slot_stride, so an explicit table travels as index = slots[i], offset 0, stride 1.
@@ -3722,31 +2407,15 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     if (n_srcs <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: n_srcs must be > 0");
     if (!items) n_items = n_srcs;
     if (n_items <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: n_items must be > 0");
-    if (!dst->data) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: dst->data is NULL");
-    if (dst->c != 3) return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_run: dst must have 3 channels (got %d)", dst->c);
-    if (dst->n <= 0 || dst->h <= 0 || dst->w <= 0)
-        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: bad dst shape %dx%dx%dx%d", dst->n, dst->c, dst->h, dst->w);
-    if (cfg->out_dtype != EVAM_DTYPE_U8 && cfg->out_dtype != EVAM_DTYPE_F32 && cfg->out_dtype != EVAM_DTYPE_F16 &&
-        cfg->out_dtype != EVAM_DTYPE_BF16)
-        return fail(EVAM_PP_ERR_UNSUPPORTED, "evam_pp_run: unknown out_dtype %d", cfg->out_dtype);
+    if (int rc = check_output("evam_pp_run", cfg, dst)) return rc;
     const bool half = cfg->out_dtype == EVAM_DTYPE_F16 || cfg->out_dtype == EVAM_DTYPE_BF16;  // 2-byte elements
-    if (cfg->resize_mode < 0 || cfg->resize_mode > 2)
-        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: unknown resize_mode %d", cfg->resize_mode);
-    if ((cfg->norm_flags & EVAM_NORM_MEAN_STD) && cfg->out_dtype != EVAM_DTYPE_U8)
-        for (int c = 0; c < 3; c++)
-            if (cfg->std[c] == 0.f) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: std[%d] == 0", c);
     const int DW = dst->w, DH = dst->h;
     const int64_t plane = (int64_t)DW * DH;
-    if (plane * 3 * (int64_t)dst->n > ((int64_t)1 << 40))
-        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: dst too large");
     const int esz = out_esz(out_kind(cfg->out_dtype));
-    // The kernels address one output plane with 32-bit byte offsets.
-    if (plane * esz > INT32_MAX)
-        return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: dst plane %dx%d exceeds 2 GiB", DW, DH);
     if (dst->layout != EVAM_LAYOUT_NCHW && dst->layout != EVAM_LAYOUT_NHWC)
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: unknown dst layout %d", dst->layout);
     const bool nhwc = dst->layout == EVAM_LAYOUT_NHWC;
-    // ... and one interleaved slot: its last element is at 3 * plane - 1.
+    // One interleaved slot is addressed with 32-bit byte offsets too: its last element is at 3 * plane - 1.
     if (nhwc && plane * 3 * esz > INT32_MAX)
         return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: interleaved dst slot %dx%dx3 exceeds 2 GiB", DH, DW);
     if (nhwc && ((uintptr_t)dst->data & (uintptr_t)(esz - 1)))
@@ -4040,14 +2709,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         // the frame half of the records, once per source (a record then takes three of its lines from here)
         std::vector<RecFrame>& rfr = h->sc_frames;
         rfr.resize((size_t)n_srcs);
-        for (int s = 0; s < n_srcs; s++) {
-            RoiRec r;
-            memset(&r, 0, sizeof(r));
-            r.plane[0] = srcs[s].planes[0]; r.plane[1] = srcs[s].planes[1]; r.plane[2] = srcs[s].planes[2];
-            r.pitch[0] = srcs[s].pitch[0]; r.pitch[1] = srcs[s].pitch[1]; r.pitch[2] = srcs[s].pitch[2];
-            r.width = (uint16_t)srcs[s].width; r.height = (uint16_t)srcs[s].height;
-            memcpy(&rfr[s], &r, sizeof(RecFrame));
-        }
+        for (int s = 0; s < n_srcs; s++) rfr[s] = rec_frame(srcs[s]);
         for (int f = 0; f < 4; f++) {
             if (path[f] != kPathRoi) continue;
             RoiRec* rr = reinterpret_cast<RoiRec*>(dyn + rec_off[f]);
@@ -4206,7 +2868,7 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
     if (h->opt_timing) HIP_TRY(hipEventRecord(h->ev0, h->stream));
     int launches = 0;
     uint32_t kmask = 0;
-    const uint32_t fill = (uint32_t)cfg->fill[0] | ((uint32_t)cfg->fill[1] << 8) | ((uint32_t)cfg->fill[2] << 16);
+    const uint32_t fill = pack_fill(cfg);
     const int color_rgb = cfg->color_order == EVAM_COLOR_RGB;
     const float* lut_d = reinterpret_cast<const float*>(d_block);
     // Kernel-argument items of one uniform launch: members [m0, m0 + n) of format group f.
@@ -4224,16 +2886,8 @@ int run_impl(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi* ite
         if (path[f] == kPathNone) continue;
         if (path[f] == kPathRoi) {
             QParams& q = qp[f];
-            q.recs = reinterpret_cast<const RoiRec*>(d_dyn + rec_off[f]);
-            q.lut = lut_d;
-            q.dst = dst->data;
-            q.mode = cfg->resize_mode;
-            q.placement = cfg->placement;
-            q.slot_offset = slot_offset;
-            q.slot_stride = slot_stride;
-            q.color_rgb = color_rgb;
-            q.fill = fill;
-            q.prio = kn.prio;
+            roi_launch_fields(q, reinterpret_cast<const RoiRec*>(d_dyn + rec_off[f]), lut_d, cfg, dst, slot_offset, slot_stride,
+                              kn.prio);
             const int64_t grid = qrec[f];
             if (grid > 0x7FFFFFFF) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_run: too many tiles");
             if (int rc = launch_kernel(qfn[f], dim3((unsigned)grid), dim3(kThreads), qlds[f], h->stream, &q, true)) return rc;
@@ -4354,230 +3008,7 @@ int evam_pp_run_slots(evam_pp* h, const evam_image* srcs, int n_srcs, const evam
 
 }  // extern "C"
 
-// ---- device-resident ROI lists ----
-namespace {
-
-int grow_device(void** p, size_t* cap, size_t n, const char* who) {
-    if (*cap >= n) return 0;
-    if (*p) {
-        HIP_TRY(hipFree(*p));  // waits for the kernels that still use it
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t c = std::max<size_t>(n * 2, 64 * 1024);
-    if (hipMalloc(p, c) != hipSuccess) {
-        *p = nullptr;
-        (void)hipGetLastError();
-        return fail(EVAM_PP_ERR_OOM, "%s: hipMalloc(%zu) failed", who, c);
-    }
-    *cap = c;
-    return 0;
-}
-
-int check_roi_list(const evam_roi_list* list, const char* who) {
-    if (!list || !list->rois || !list->count) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: NULL ROI list pointer", who);
-    if (list->cap <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: list cap %d must be > 0", who, list->cap);
-    return 0;
-}
-
-int check_ssd_args(const char* who, const float* det, int n_items, int k, const evam_image* srcs, int tensor_w,
-                   int tensor_h, const int32_t* labels, int n_labels, const evam_roi_list* list) {
-    if (!det || !srcs) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (int rc = check_roi_list(list, who)) return rc;
-    if (n_items <= 0 || k <= 0 || n_items > 65535 || k > 65535)
-        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: n_items %d / k %d outside 1..65535", who, n_items, k);
-    if (tensor_w <= 0 || tensor_h <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad tensor size %dx%d", who, tensor_w, tensor_h);
-    if (n_labels < 0 || (!labels && n_labels > 0)) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad label list", who);
-    for (int i = 0; i < n_items; i++)
-        if (srcs[i].width <= 0 || srcs[i].height <= 0 || srcs[i].width > 32768 || srcs[i].height > 32768)
-            return fail(EVAM_PP_ERR_INVALID_ARG, "%s: srcs[%d] bad size %dx%d", who, i, srcs[i].width, srcs[i].height);
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int evam_pp_ssd_rois_host(const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
-                          int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
-                          const evam_roi_list* list) {
-    if (int rc = check_ssd_args("evam_pp_ssd_rois_host", det, n_items, k, srcs, tensor_w, tensor_h, labels, n_labels, list))
-        return rc;
-    static const int32_t none = 0;
-    const int32_t* lab = labels ? (n_labels ? labels : &none) : nullptr;
-    uint32_t total = 0;
-    for (int i = 0; i < n_items; i++) {
-        const float* d = det + (size_t)i * (size_t)k * 7;
-        for (int r = 0; r < k; r++) {
-            const float* row = d + (size_t)r * 7;
-            if (row[0] < 0.f) break;
-            int x, y, w, h;
-            if (!ssd_row_rect(row, xf ? xf + i : nullptr, srcs[i].width, srcs[i].height, tensor_w, tensor_h, threshold, lab,
-                              n_labels, x, y, w, h))
-                continue;
-            if (total < (uint32_t)list->cap) list->rois[total] = evam_roi{i, x, y, w, h};
-            total++;
-        }
-    }
-    *list->count = total;
-    return EVAM_PP_OK;
-}
-
-int evam_pp_ssd_rois(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
-                     int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
-                     const evam_roi_list* list) {
-    return evam_pp_ssd_rois_ex(h, det, n_items, k, srcs, xf, tensor_w, tensor_h, threshold, labels, n_labels, list, nullptr);
-}
-
-int evam_pp_ssd_rois_ex(evam_pp* h, const float* det, int n_items, int k, const evam_image* srcs, const evam_transform* xf,
-                        int tensor_w, int tensor_h, float threshold, const int32_t* labels, int n_labels,
-                        const evam_roi_list* list, int32_t* out_labels) {
-    if (!h) return fail(EVAM_PP_ERR_INVALID_ARG, "evam_pp_ssd_rois: NULL handle");
-    if (int rc = check_ssd_args("evam_pp_ssd_rois", det, n_items, k, srcs, tensor_w, tensor_h, labels, n_labels, list))
-        return rc;
-    // host block: [int2 x n_items: frame sizes][evam_transform x n_items, with xf][int32 x n_labels] (never empty)
-    const size_t off_xf = sizeof(int2) * (size_t)n_items;
-    const size_t off_lab = off_xf + (xf ? sizeof(evam_transform) * (size_t)n_items : 0);
-    std::vector<uint8_t>& blk = h->h_aux;
-    blk.assign(off_lab + sizeof(int32_t) * (size_t)std::max(1, n_labels), 0);
-    for (int i = 0; i < n_items; i++) {
-        const int32_t wh[2] = {srcs[i].width, srcs[i].height};
-        memcpy(blk.data() + sizeof(int2) * (size_t)i, wh, sizeof(wh));
-    }
-    if (xf) memcpy(blk.data() + off_xf, xf, sizeof(evam_transform) * (size_t)n_items);
-    if (n_labels) memcpy(blk.data() + off_lab, labels, sizeof(int32_t) * (size_t)n_labels);
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = grow_device(&h->dev_cnt, &h->dev_cnt_cap, 2 * sizeof(uint32_t) * (size_t)n_items, "evam_pp_ssd_rois")) return rc;
-    const uint8_t* d_blk = nullptr;
-    {
-        HipRings b;
-        if (int rc = h->ring_ssd.upload(b, h->stream, blk.data(), blk.size(), &d_blk)) return rc;
-    }
-    SsdParams p{};
-    p.det = det;
-    p.sizes = reinterpret_cast<const int2*>(d_blk);
-    p.xf = xf ? reinterpret_cast<const evam_transform*>(d_blk + off_xf) : nullptr;
-    p.labels = labels ? reinterpret_cast<const int32_t*>(d_blk + off_lab) : nullptr;
-    p.item_count = static_cast<uint32_t*>(h->dev_cnt);
-    p.item_off = p.item_count + n_items;
-    p.rois = list->rois;
-    p.count = list->count;
-    p.n_items = n_items; p.k = k; p.n_labels = n_labels;
-    p.TW = tensor_w; p.TH = tensor_h; p.cap = list->cap;
-    p.threshold = threshold;
-    p.out_labels = out_labels;
-    hipLaunchKernelGGL((evam_pp_ssd_rows<false>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
-    hipLaunchKernelGGL(evam_pp_ssd_scan, dim3(1), dim3(kThreads), 0, h->stream, p.item_count, p.item_off, n_items, p.count);
-    if (out_labels) hipLaunchKernelGGL((evam_pp_ssd_rows<true, true>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
-    else hipLaunchKernelGGL((evam_pp_ssd_rows<true>), dim3(n_items), dim3(kThreads), 0, h->stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "evam_pp_ssd_rois: kernel launch failed: %s", hipGetErrorString(e));
-    return EVAM_PP_OK;
-}
-
-int evam_pp_run_device_rois(evam_pp* h, const evam_image* srcs, int n_srcs, const evam_roi_list* list,
-                            const evam_preproc* cfg, const evam_tensor* dst, int32_t* status) {
-    const char* who = "evam_pp_run_device_rois";
-    if (!h || !srcs || !cfg || !dst) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (int rc = check_roi_list(list, who)) return rc;
-    if (n_srcs <= 0) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: n_srcs must be > 0", who);
-    if (!dst->data) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst->data is NULL", who);
-    if (dst->c != 3) return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: dst must have 3 channels (got %d)", who, dst->c);
-    if (dst->n <= 0 || dst->h <= 0 || dst->w <= 0)
-        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: bad dst shape %dx%dx%dx%d", who, dst->n, dst->c, dst->h, dst->w);
-    if (cfg->out_dtype != EVAM_DTYPE_U8 && cfg->out_dtype != EVAM_DTYPE_F32 && cfg->out_dtype != EVAM_DTYPE_F16 &&
-        cfg->out_dtype != EVAM_DTYPE_BF16)
-        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: unknown out_dtype %d", who, cfg->out_dtype);
-    if (cfg->resize_mode < 0 || cfg->resize_mode > 2)
-        return fail(EVAM_PP_ERR_INVALID_ARG, "%s: unknown resize_mode %d", who, cfg->resize_mode);
-    if ((cfg->norm_flags & EVAM_NORM_MEAN_STD) && cfg->out_dtype != EVAM_DTYPE_U8)
-        for (int c = 0; c < 3; c++)
-            if (cfg->std[c] == 0.f) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: std[%d] == 0", who, c);
-    const int DW = dst->w, DH = dst->h, cap = list->cap;
-    const int64_t plane = (int64_t)DW * DH;
-    const int esz = out_esz(out_kind(cfg->out_dtype));
-    if (plane * 3 * (int64_t)dst->n > ((int64_t)1 << 40)) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst too large", who);
-    if (plane * esz > INT32_MAX) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: dst plane %dx%d exceeds 2 GiB", who, DW, DH);
-    if (dst->layout == EVAM_LAYOUT_NHWC)
-        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: interleaved (NHWC) output is not served from a device list", who);
-    if (dst->layout != EVAM_LAYOUT_NCHW) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: unknown dst layout %d", who, dst->layout);
-    for (int i : {0, cap - 1}) {  // slots are linear in the entry index: the first and the last bound them all
-        const int64_t slot = (int64_t)dst->slot_offset + (int64_t)i * dst->slot_stride;
-        if (slot < 0 || slot >= dst->n)
-            return fail(EVAM_PP_ERR_INVALID_ARG, "%s: entry %d -> slot %lld outside tensor batch %d", who, i, (long long)slot, dst->n);
-    }
-    if (int rc = validate_sources(srcs, n_srcs)) return rc;
-    const int f = fmt_id(srcs[0].fourcc);
-    int max_w = 0;
-    for (int i = 0; i < n_srcs; i++) {
-        if (fmt_id(srcs[i].fourcc) != f)
-            return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: sources of more than one format in a call (srcs[%d])", who, i);
-        max_w = std::max(max_w, srcs[i].width);
-    }
-    // Planned without the rects: staging for the widest source, occupancy from the list's capacity, units in list order.
-    const Knobs& kn = h->knobs;
-    QParams q{};
-    int base = 1, lds = 0;
-    int64_t slots = 0;
-    const void* fn = nullptr;
-    HIP_TRY(hipSetDevice(h->device));
-    if (!plan_roi(HipKernels{}, f, DW, DH, cfg->out_dtype, kn.roi_px, row_bytes_bound(f, max_w), cap, h->n_cu, kn, q, base, lds,
-                  slots, fn, true))
-        return fail(EVAM_PP_ERR_UNSUPPORTED, "%s: %dx%d output from %d-wide sources is not planned by the ROI kernel", who, DW,
-                    DH, max_w);
-    const int64_t units = (int64_t)cap * base;
-    if (units > 0x7FFFFFFF - kThreads) return fail(EVAM_PP_ERR_INVALID_ARG, "%s: too many tiles", who);
-    // host block: [LUT][RecFrame x n_srcs]
-    std::vector<uint8_t>& blk = h->h_aux;
-    blk.resize(kLutBytes + sizeof(RecFrame) * (size_t)n_srcs);
-    block_lut(h, cfg, blk.data());
-    for (int s = 0; s < n_srcs; s++) {
-        RoiRec r;
-        memset(&r, 0, sizeof(r));
-        for (int p = 0; p < 3; p++) { r.plane[p] = srcs[s].planes[p]; r.pitch[p] = srcs[s].pitch[p]; }
-        r.width = (uint16_t)srcs[s].width; r.height = (uint16_t)srcs[s].height;
-        memcpy(blk.data() + kLutBytes + sizeof(RecFrame) * (size_t)s, &r, sizeof(RecFrame));
-    }
-    if (int rc = grow_device(&h->dev_recs, &h->dev_recs_cap, sizeof(RoiRec) * (size_t)units, who)) return rc;
-    const uint8_t* d_blk = nullptr;
-    {
-        HipRings b;
-        if (int rc = h->ring.upload(b, h->stream, blk.data(), blk.size(), &d_blk)) return rc;
-    }
-    if (h->opt_timing) HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    DParams d{};
-    d.rois = list->rois;
-    d.count = list->count;
-    d.srcs = reinterpret_cast<const uint4*>(d_blk + kLutBytes);
-    d.recs = static_cast<RoiRec*>(h->dev_recs);
-    d.status = status;
-    d.cap = cap; d.n_srcs = n_srcs; d.tiles = base; d.TH = q.TH; d.DH = DH; d.fmt = f;
-    hipLaunchKernelGGL(evam_pp_roi_records, dim3((unsigned)((units + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, d);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(EVAM_PP_ERR_HIP, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
-    q.recs = d.recs;
-    q.lut = reinterpret_cast<const float*>(d_blk);
-    q.dst = dst->data;
-    q.mode = cfg->resize_mode;
-    q.placement = cfg->placement;
-    q.slot_offset = dst->slot_offset;
-    q.slot_stride = dst->slot_stride;
-    q.color_rgb = cfg->color_order == EVAM_COLOR_RGB;
-    q.fill = (uint32_t)cfg->fill[0] | ((uint32_t)cfg->fill[1] << 8) | ((uint32_t)cfg->fill[2] << 16);
-    q.prio = kn.prio;
-    if (int rc = launch_kernel(fn, dim3((unsigned)units), dim3(kThreads), lds, h->stream, &q, true)) return rc;
-    if (h->opt_timing) HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    h->timed = h->opt_timing != 0;
-    h->stats.n_items = cap;
-    h->stats.n_launches = 2;
-    h->stats.kernels = EVAM_KERNEL_ROI;
-    h->stats.src_bytes = 0;
-    h->stats.dst_bytes = (int64_t)cap * plane * 3 * esz;
-    return EVAM_PP_OK;
-}
-
-}  // extern "C"
-
+#include "evam_rois_api.h"
 #include "evam_jpeg_api.h"
 #include "evam_jpeg_dec_api.h"
 #include "evam_track_api.h"

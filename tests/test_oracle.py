@@ -178,7 +178,7 @@ def test_nv12_equals_i420_same_samples(O, coracle):
 
 
 def test_saturating_clamp_identity():
-    """The kernels' packed saturating clamp (evam_pp.hip hpass_sat) equals clamp255(S >> 20) on all (Y, U, V)."""
+    """The kernels' packed saturating clamp (evam_kernel_common.h hpass_sat) equals clamp255(S >> 20) on all (Y, U, V)."""
     import importlib.util
     import os
     spec = importlib.util.spec_from_file_location(

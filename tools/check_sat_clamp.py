@@ -1,4 +1,4 @@
-"""Exhaustive check of the saturating BT.601 clamp used by the HIP kernels (evam_pp.hip, hpass_sat).
+"""Exhaustive check of the saturating BT.601 clamp used by the HIP kernels (csrc/evam_kernel_common.h, hpass_sat).
 
 For every (Y, U, V) byte triple and every channel, the kernel computes
     s   = min(y + term', 2^32 - 1)                (v_add_u32 clamp)
