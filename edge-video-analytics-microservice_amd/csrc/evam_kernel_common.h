@@ -1,7 +1,7 @@
 // Device helpers that two or more kernel families use: the diagnostic and cache-policy macros, the exact OpenCV
 // arithmetic, the saturating BT.601 form, the store helpers, LaneRows, lds_barrier, ProgressPrio and the trace macros.
-// Included by evam_pp.hip before any kernel family, in the file or in a header (evam_strip_kernels.h,
-// evam_band_kernels.h); reopens its anonymous namespace (evam:: names).
+// Included by evam_pp.hip before the kernel families' headers (evam_{generic,rows,staged,wave,strip,band,roi}_kernels.h);
+// reopens its anonymous namespace (evam:: names).
 #pragma once
 
 namespace {

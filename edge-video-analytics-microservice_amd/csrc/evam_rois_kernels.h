@@ -1,6 +1,6 @@
 // Device-resident ROI lists: evam_pp_roi_records (list -> ROI-kernel records) and evam_pp_ssd_rows / evam_pp_ssd_scan
 // (SSD rows -> list). Included by evam_pp.hip after the kernel families; reopens its anonymous namespace. Entry points
-// in evam_rois_api.h.
+// in evam_rois_api.h. Not evam_roi_kernels.h (singular): that header is evam_pp_roi, the kernel these records feed.
 #pragma once
 
 namespace {
